@@ -22,11 +22,25 @@ products, include/pnr_abi.h); `dtype` stays "f32" (fp32 in / out / accumulation)
 Inputs are synthetic (hash-initialised MLP weights, random-init encoder, hashed source
 image), resident in HBM when the timed region starts.
 
-The JSON line also carries
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: set up, W warm-up steps,
+K timed steps, one JSON line (`value`, `ms_per_step`, and the figures below that come from the
+timed steps themselves: `roofline`, `kernel_ms`, `encode_ms`, `box_clock`, `l2_stream`).
+`--dump-outputs DIR` also writes what the last timed step returned to its caller, the rank's
+rendered rgb (rays x 3, float32) as it landed in host memory, to DIR/rgb.npy
+(DIR/rgb_rank<r>.npy at N > 1).  The inputs are seeded / hashed, so two runs with the same
+arguments render the same batch and two builds can be compared output for output (to ~1e-4
+of an rgb in [0, 1], not bit for bit: MIOpen may pick another convolution algorithm in another
+process, which moves the random-init encoder's latent in its last bits; measured max |d| 5e-4
+between runs of one build).
+`--full` adds every further leg (train, cfg2, composite, extra_configs, cpu_baseline,
+psnr_vs_reference_path; each still has its --no-* switch).
+
+The JSON line carries
   roofline     -- the dominant kernel (fine-pass fused point MLP, k_point_mlp): its
                   algorithmic FLOP per launch / its mean launch duration, both from HIP
                   events recorded on the launch stream around every kernel inside the timed
                   region; `traffic` from the committed rocprofv3 PMC pass;
+and with --full
   train        -- cfg5 (BASELINE configs[4]): the training step (encoder, coarse + fine
                   render, backward, bucketed RCCL gradient all-reduce, Adam), 4 x 256 rays
                   per rank (weak scaling: 8 ranks = 8192 rays), at every N;
@@ -335,7 +349,9 @@ def make_net(dev, precision, latent_proj, use_first_pool=True):
     return net
 
 
-def cfg3_leg(args, dev, rank, world, probe, clock=None):
+def cfg3_leg(args, dev, rank, world, probe, clock=None, outputs=None):
+    """The headline leg.  `outputs` (a dict) receives what the last timed step handed to its
+    caller: "rgb", the rank's shard in host memory."""
     net = make_net(dev, args.precision, not args.no_latent_proj, use_first_pool=False)
     # the eval encode runs the BN-folded trunk replayed as one HIP graph (pnr.encoder.InferenceTrunk);
     # --encoder-eager: the module's own conv / BN / relu launches (A/B)
@@ -368,6 +384,8 @@ def cfg3_leg(args, dev, rank, world, probe, clock=None):
         elapsed, rgb = timed(step, args.steps, 0, dev, world, clock=clock)
         probe.on = False
     assert bool(torch.isfinite(rgb).all())
+    if outputs is not None:
+        outputs["rgb"] = host.clone()   # timed() synchronised: the last step's copy has landed
     avg, roof = probe.summary(args.precision, net.use_latent_proj)
     enc = enc_ev[0].elapsed_time(enc_ev[1])   # the last timed step's encode
     return net, (img, src, focal, rays), elapsed, avg, roof, enc, (start, end)
@@ -969,6 +987,18 @@ def psnr_vs_reference_path(net, rays_dev, ref, streams, dev, sd, scene, white_bk
     return res
 
 
+# ----------------------------------------------------------------- outputs -----------
+def dump_outputs(path, outputs, rank, world):
+    """--dump-outputs: every array of `outputs` as <path>/<name>.npy (float32, C order); with more
+    than one rank each writes its own shard as <name>_rank<r>.npy."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        arr = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), arr)
+
+
 # ----------------------------------------------------------------- launcher ----------
 def _free_port():
     import socket
@@ -1017,6 +1047,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also run the train (cfg5), cfg2, composite, extra-config, CPU "
+                         "baseline and oracle-agreement legs (each has its --no-* switch); a plain run times the "
+                         "headline leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the rank's rgb, float32) to DIR/rgb.npy "
+                         "(DIR/rgb_rank<r>.npy with more than one rank)")
     ap.add_argument("--cpu-rays", type=int, default=512, help="oracle sample of the headline batch")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-composite", action="store_true")
@@ -1058,7 +1095,10 @@ def main():
     probe = RenderProbe(ev)
 
     clock = None if args.no_clock else ClockSampler(dev)
-    net3, nmr, elapsed, avg, roof, enc_ms, (start, end) = cfg3_leg(args, dev, rank, world, probe, clock)
+    outputs = {} if args.dump_outputs else None
+    net3, nmr, elapsed, avg, roof, enc_ms, (start, end) = cfg3_leg(args, dev, rank, world, probe, clock, outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
     n_batch = nmr[3].shape[0]
     pmc_path, same_lease = pmc_summary_path(args.traffic_from)
     roof["traffic"] = pmc_traffic(roof["kernel_name"], "fine", "cfg3", pmc_path)
@@ -1070,6 +1110,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(1e3 * elapsed / args.steps, 3),
         "higher_is_better": True,
         "scaling": "strong",
@@ -1102,9 +1143,9 @@ def main():
         "l2_stream": l2_stream(roof["points_per_launch"], roof["launch_ms"], args.precision,
                                not args.no_latent_proj),
     }
-    if not args.no_train:
+    if args.full and not args.no_train:
         out["train"] = train_leg(dev, rank, world, args.train_steps, 2, precision=args.precision)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cfg2:
             out["cfg2"] = cfg2_leg(args, dev, probe)
         if not args.no_composite:

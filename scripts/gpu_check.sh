@@ -14,6 +14,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_ou
 rc=$?; echo "smoke rc=$rc"; tail -5 gpurun_out/smoke.log
 ok $rc || exit $rc
 [ -n "$NO_BENCH" ] && exit 0
+BENCH_ARGS="--full ${BENCH_ARGS}"   # every leg of the bench, not the headline alone
 echo "== bench"; date
 timeout -k 10 600 python bench.py --steps ${BENCH_STEPS:-5} --warmup 1 ${BENCH_ARGS} > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -c 3000 gpurun_out/bench.log

@@ -20,6 +20,7 @@ TAG=${1:?tag}; shift
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 PY=python3
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the bench and evidence steps run every leg of the bench
 run() {  # run <timeout_s> <log> <cmd...>
   local t=$1 log=$2; shift 2
   echo "== $(date +%T) $*"
@@ -40,7 +41,7 @@ for step in "$@"; do
     evidence)
       P=$REPO/gpurun_out/prof_$TAG
       mkdir -p $P
-      LEG="--steps 1 --warmup 0 --no-cpu --no-compare --no-extra --no-train --no-cfg2 --no-clock"
+      LEG="--full --steps 1 --warmup 0 --no-cpu --no-compare --no-extra --no-train --no-cfg2 --no-clock"
       export TMPDIR=/tmp
       for ctr in FETCH_SIZE WRITE_SIZE GRBM_GUI_ACTIVE; do
         ( cd /tmp && run 300 $P/pmc_$ctr.log rocprofv3 --pmc $ctr --output-format csv -d $P/pmc_$ctr -o run -- \

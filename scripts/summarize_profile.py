@@ -81,7 +81,7 @@ def main():
     if os.path.exists(os.path.join(src, "trace", "run_kernel_stats.csv")):
         trace_stats(src, dst)
     lines = [
-        "# rocprofv3 PMC summary, %s (bench.py cfg3 headline leg + the 1 M-ray composite leg, --steps 1 --warmup 0) %s" % (tag, note),
+        "# rocprofv3 PMC summary, %s (bench.py cfg3 headline leg + the 1 M-ray composite leg, --full --steps 1 --warmup 0) %s" % (tag, note),
         "# FETCH_SIZE/WRITE_SIZE in KB as rocprofv3 reports them (per dispatch).",
         "# gfx950: FETCH_SIZE reads 1/2 of wide coalesced streaming reads (MI355X_MICROARCH.md HBM)"
         " -> corrected = 2x.",

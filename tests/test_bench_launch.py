@@ -30,6 +30,22 @@ def test_check_world():
         bench.check_world(4, env={"WORLD_SIZE": "2"})
 
 
+def test_dump_outputs_writes_float32_npy_per_rank(tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float32 for a single rank, <name>_rank<r>.npy per rank
+    otherwise; the directory is created."""
+    import numpy as np
+    import torch
+
+    rgb = torch.arange(12, dtype=torch.float64).reshape(4, 3) / 7
+    bench.dump_outputs(str(tmp_path / "a" / "b"), {"rgb": rgb}, 0, 1)
+    got = np.load(tmp_path / "a" / "b" / "rgb.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 3)
+    np.testing.assert_array_equal(got, rgb.numpy().astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "c"), {"rgb": rgb[2:].float()}, 1, 2)
+    assert sorted(os.listdir(tmp_path / "c")) == ["rgb_rank1.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "rgb_rank1.npy"), rgb[2:].float().numpy())
+
+
 def test_spawned_ranks_reach_rank_code(tmp_path):
     """End to end on the CPU: the parent builds the launcher command and the child
     torch.distributed.run starts 2 ranks of a stand-in script that reports its env; the

@@ -12,7 +12,7 @@ for round in $(seq ${ROUNDS:-2}); do
     lib=pixel-nerf_amd/build/$t/libpnr.so
     [ "$t" = default ] && lib=pixel-nerf_amd/pnr/libpnr.so
     echo -n "$v: "
-    PNR_LIB_PATH=$lib timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu --no-extra $comp \
+    PNR_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu --no-extra $comp \
         --no-compare --no-train $extra 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); c = d['cfg2']; k = d['kernel_ms']
