@@ -82,8 +82,25 @@ typedef struct pnr_mlp_desc {
  *                   (max <= 2^14), each split into two fp16 parts x = x0 + x1 (|x - x0 - x1|
  *                   <= 2^-22 |x|); 3 exact products x0 y0 + x0 y1 + x1 y0 on
  *                   v_mfma_f32_16x16x32_f16, fp32 accumulation, scales undone exactly.
- *                   Error at the fp32 level (tools/precision_study.py). */
+ *                   Error at the fp32 level (tools/precision_study.py).
+ *   PNR_PREC_F16    half precision, INFERENCE ONLY (additive in ABI 8).  The same scaling as
+ *                   F16X3 (W per layer and every activation column by a power of two, max
+ *                   <= 2^14, so the mode is safe at any dynamic range), but each operand of the
+ *                   512 -> 512 layers is rounded ONCE to fp16 (round to nearest even): one
+ *                   product per k-step on v_mfma_f32_16x16x32_f16, fp32 accumulation, scales
+ *                   undone exactly.  The pack of those layers holds one fp16 part (half of
+ *                   F16X3's layer bytes).  lin_in (d_in <= 64), the lin_z contribution (the
+ *                   fp32 projected latent), the multi-view mean and the head keep F16X3's /
+ *                   fp32 arithmetic.  Error: one fp16 rounding (2^-11 relative) per operand
+ *                   and layer; on the pixelNeRF fixtures max |d rgb| 6e-4 per point and 4e-4
+ *                   per ray, max |d sigma| 2.6e-3, against an 8-bit step of 3.9e-3
+ *                   (tests/f16_emul.py).  It runs on the projected-latent path
+ *                   only: pnr_point_query_proj / pnr_render_forward_proj with the latent
+ *                   projections; a call without them, the training forward (activation save),
+ *                   pnr_mlp_packed_t_bytes / pnr_mlp_pack_t and pnr_mlp_backward refuse it
+ *                   (PNR_ERR_UNSUPPORTED, 0 bytes). */
 #define PNR_PREC_F32 0
+#define PNR_PREC_F16 1
 #define PNR_PREC_F16X3 3
 #define PNR_PREC_BF16X6 6
 #define PNR_PREC_BF16X9 9

@@ -19,6 +19,13 @@
 //     W is pre-packed (k_pack_f16) in A-fragment order with a per-layer scale and streamed
 //     from L2 through a register ring H_DIST row tiles ahead of v_mfma_f32_16x16x32_f16.
 //     fp32 (PREC 0) and split-bf16 (PREC 6 / 9) keep an fp32 image and their own GEMMs.
+//   * f16 (PREC 1, inference on the projected-latent path only): the f16x3 schedule with ONE
+//     part in every 512 -> 512 layer: W 2^eW and relu(acc) 2^e_col are each rounded once to fp16
+//     (RNE), one v_mfma_f32_16x16x32_f16 product per k-step, fp32 accumulation, the scales undone
+//     exactly.  The weight stream of those layers is single-part (half of f16x3's bytes) and the
+//     publish writes P0 only.  Left as in f16x3: lin_in (2 k-steps, d_in 42: two-part features
+//     and weights, three products), the lin_z contribution (the fp32 projected latent), the
+//     multi-view mean and the head (fp32 from the accumulators).
 // Diagnostic build knobs: pnr_diag.h.
 #include "pnr_diag.h"
 #include <cstddef>
@@ -51,10 +58,22 @@ constexpr int SRT16_FLOATS = 512;
 constexpr int SKS16_FLOATS = NRT * SRT16_FLOATS;  // 64 KB
 constexpr int HDR_ESCALE = 32;     // header floats [32, 64): per-layer weight scale exponents
                                    // (PREC 3): [32] lin_in, [33 + j] packed 512-wide layer j
-__host__ __device__ constexpr int sks_floats(int prec) { return prec == 3 ? SKS16_FLOATS : SKS_FLOATS; }
+// half-precision modes: 3 = f16x3 (two parts), 1 = f16 (one part in the 512-wide layers)
+__host__ __device__ constexpr bool is_h(int prec) { return prec == 3 || prec == 1; }
+__host__ __device__ constexpr int nparts(int prec) { return prec == 1 ? 1 : 2; }
+// floats of one (k-step, row tile) / one k-step of an NP-part fp16 layer: NP x 64 lanes x 8 f16
+__host__ __device__ constexpr int srt_h_floats(int np) { return np * 256; }
+__host__ __device__ constexpr int sks_h_floats(int np) { return NRT * srt_h_floats(np); }
+static_assert(srt_h_floats(2) == SRT16_FLOATS && sks_h_floats(2) == SKS16_FLOATS, "two-part layout");
+// 512-wide layers: PREC 1 streams one part; lin_in keeps the two-part layout in both fp16 modes
+__host__ __device__ constexpr int sks_floats(int prec) {
+    return prec == 3 ? SKS16_FLOATS : prec == 1 ? sks_h_floats(1) : SKS_FLOATS;
+}
+__host__ __device__ constexpr int sks_in_floats(int prec) { return is_h(prec) ? SKS16_FLOATS : SKS_FLOATS; }
 
 struct Layout {
-    int prec;                      // 0 = f32 MFMA, 6 / 9 = split-bf16 products, 3 = scaled f16
+    int prec;                      // 0 = f32 MFMA, 6 / 9 = split-bf16 products, 3 = scaled f16 (two parts),
+                                   // 1 = scaled f16 (one part)
     int n_linz, n_l512, n_blocks, ncomb, d_in, d_out, pe_n;
     int64_t layer_floats;
     int64_t off_lin_in, off_l512, off_lin_out, off_bias, nbias, off_out32, total;
@@ -72,13 +91,13 @@ inline Layout make_layout(const pnr_mlp_desc &d) {
     L.prec = d.precision;
     L.layer_floats = L.prec ? (int64_t)KS32 * sks_floats(L.prec) : (int64_t)LAYER_FLOATS;
     L.off_lin_in = HDR;
-    L.off_l512 = L.off_lin_in + (L.prec ? (int64_t)KS32_IN * sks_floats(L.prec) : (int64_t)NKB_IN * KB_FLOATS);
+    L.off_l512 = L.off_lin_in + (L.prec ? (int64_t)KS32_IN * sks_in_floats(L.prec) : (int64_t)NKB_IN * KB_FLOATS);
     L.off_lin_out = L.off_l512 + (int64_t)L.n_l512 * L.layer_floats;
     L.off_bias = L.off_lin_out + (int64_t)NKB * 256;
     L.nbias = (int64_t)(1 + L.n_l512) * H + 16;
-    // PREC 3: lin_out's weights in fp32 as [input channel][4 outputs] (the VALU head, k_point_mlp)
+    // PREC 3 / 1: lin_out's weights in fp32 as [input channel][4 outputs] (the VALU head, k_point_mlp)
     L.off_out32 = ((L.off_bias + L.nbias + 63) / 64) * 64;
-    L.total = L.off_out32 + (L.prec == 3 ? 4 * H : 0);
+    L.total = L.off_out32 + (is_h(L.prec) ? 4 * H : 0);
     return L;
 }
 
@@ -100,7 +119,7 @@ __global__ void k_pack(PackSrc s, Layout L, float *__restrict__ out) {
     if (i >= L.total) return;
     float v = 0.0f;
     if (i < HDR) {
-        if (i >= HDR_ESCALE && i < HDR_ESCALE + 1 + L.n_l512 && L.prec == 3) return;   // k_layer_escale's
+        if (i >= HDR_ESCALE && i < HDR_ESCALE + 1 + L.n_l512 && is_h(L.prec)) return;   // k_layer_escale's
         if (i < 16 && i < L.pe_n) v = s.pe_f[i];
         else if (i >= 16 && i < 32 && (i - 16) < L.pe_n) v = s.pe_p[i - 16];
     } else if (i < L.off_lin_out && L.prec) {
@@ -219,6 +238,8 @@ __global__ void k_layer_escale(int n_slots, float *__restrict__ out) {
 // One thread per (layer, k-step, row tile, lane): 8 weights w * 2^eW, each split
 // into two fp16 parts w0 = f16(w), w1 = f16(w - w0) (RNE), [ks][rt][part][lane][8].
 // (lin_out is not split: the head reads it in fp32 from off_out32.)
+// PREC 1: the 512-wide layers hold w0 only, [ks][rt][lane][8] (half the bytes: the stream's L2
+// footprint is the point of the mode); lin_in keeps both parts.
 __global__ void k_pack_f16(PackSrc s, Layout L, float *__restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n_in = (int64_t)KS32_IN * NRT * 64;
@@ -236,8 +257,10 @@ __global__ void k_pack_f16(PackSrc s, Layout L, float *__restrict__ out) {
         layer = (int)(r / n_l);
         const int64_t e = r % n_l;
         ks = (int)(e / (NRT * 64)); rt = (int)((e / 64) % NRT); lane = (int)(e % 64);
-        dst = out + L.off_l512 + layer * L.layer_floats + (int64_t)ks * SKS16_FLOATS + rt * SRT16_FLOATS + lane * 4;
+        dst = out + L.off_l512 + layer * L.layer_floats + (int64_t)ks * sks_floats(L.prec) +
+              rt * srt_h_floats(nparts(L.prec)) + lane * 4;
     }
+    const int np = layer < 0 ? 2 : nparts(L.prec);
     const int ew = (int)out[HDR_ESCALE + 1 + layer];
     const int row = 16 * rt + (lane & 15);
     _Float16 p[2][8];
@@ -254,6 +277,7 @@ __global__ void k_pack_f16(PackSrc s, Layout L, float *__restrict__ out) {
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
+        if (q >= np) break;
         typedef _Float16 h8t __attribute__((ext_vector_type(8)));
         h8t v = {p[q][0], p[q][1], p[q][2], p[q][3], p[q][4], p[q][5], p[q][6], p[q][7]};
         *reinterpret_cast<h8t *>(dst + q * 256) = v;
@@ -619,24 +643,25 @@ constexpr int H_DIST = 4;          // f16 weight prefetch distance (row tiles), 
 // in slot t % slots.  hring_prime issues the first DIST row tiles; gemm_f16_primed runs the
 // layer on a primed ring.  Priming the next layer's ring before the publish that precedes it
 // (k_point_mlp) lets those loads' L2 latency pass under the publish and its LDS-only barriers.
-template <int DIST>
+// NP: parts per slot (2: f16x3's w0 / w1; 1: the single-part layers of PREC 1)
+template <int DIST, int NP = 2>
 struct HRing {
     static constexpr int slots = DIST < RTW ? RTW : 2 * RTW;
-    h8 ra[slots][2];
+    h8 ra[slots][NP];
 };
 
-template <int DIST>
-__device__ __forceinline__ void hring_load(HRing<DIST> &R, const float *__restrict__ wp, int slot, int ks, int r) {
+template <int DIST, int NP>
+__device__ __forceinline__ void hring_load(HRing<DIST, NP> &R, const float *__restrict__ wp, int slot, int ks, int r) {
 #ifdef PNR_ABLATE_WSTREAM
     ks = 0;  // diagnostic: no weight stream
 #endif
-    const float *src = wp + (int64_t)ks * SKS16_FLOATS + r * SRT16_FLOATS;
+    const float *src = wp + (int64_t)ks * sks_h_floats(NP) + r * srt_h_floats(NP);
     R.ra[slot][0] = *reinterpret_cast<const h8 *>(src);
-    R.ra[slot][1] = *reinterpret_cast<const h8 *>(src + 256);
+    if constexpr (NP > 1) R.ra[slot][1] = *reinterpret_cast<const h8 *>(src + 256);
 }
 
-template <int DIST, int NKS = KS32>
-__device__ __forceinline__ void hring_prime(HRing<DIST> &R, const float *__restrict__ wp) {
+template <int DIST, int NKS = KS32, int NP = 2>
+__device__ __forceinline__ void hring_prime(HRing<DIST, NP> &R, const float *__restrict__ wp) {
 #pragma unroll
     for (int t = 0; t < DIST; ++t) hring_load(R, wp, t, (t / RTW) & (NKS - 1), t % RTW);
 }
@@ -650,10 +675,10 @@ struct Fair {
     int *prog;   // LDS: iteration count per wave (8 ints)
     int wave, it, mate;
 };
-template <int NKS, int DIST = H_DIST>
-__device__ __forceinline__ void gemm_f16_primed(Acc &acc, HRing<DIST> &R, const float *__restrict__ wp,
+template <int NKS, int DIST = H_DIST, int NP = 2>
+__device__ __forceinline__ void gemm_f16_primed(Acc &acc, HRing<DIST, NP> &R, const float *__restrict__ wp,
                                                 const _Float16 *pb0, const _Float16 *pb1, Fair *F = nullptr) {
-    constexpr int H_RING = HRing<DIST>::slots;   // register ring slots
+    constexpr int H_RING = HRing<DIST, NP>::slots;   // register ring slots
     static_assert(DIST < H_RING && H_RING % RTW == 0, "ring");
     constexpr int U = H_RING / RTW;   // k-steps per loop iteration (static ring slots)
     static_assert(NKS % U == 0, "k-steps");
@@ -667,7 +692,7 @@ __device__ __forceinline__ void gemm_f16_primed(Acc &acc, HRing<DIST> &R, const 
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             b0[c] = *reinterpret_cast<const h8 *>(pb0 + c * 16 * ROWH + 32 * kr);
-            b1[c] = *reinterpret_cast<const h8 *>(pb1 + c * 16 * ROWH + 32 * kr);
+            if constexpr (NP > 1) b1[c] = *reinterpret_cast<const h8 *>(pb1 + c * 16 * ROWH + 32 * kr);
         }
 #pragma unroll
         for (int r = 0; r < RTW; ++r) {
@@ -679,8 +704,10 @@ __device__ __forceinline__ void gemm_f16_primed(Acc &acc, HRing<DIST> &R, const 
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 f4 v = acc[r][c];
-                v = mfma_h(a[1], b0[c], v);
-                v = mfma_h(a[0], b1[c], v);
+                if constexpr (NP > 1) {
+                    v = mfma_h(a[1], b0[c], v);
+                    v = mfma_h(a[0], b1[c], v);
+                }
                 v = mfma_h(a[0], b0[c], v);
                 acc[r][c] = v;
             }
@@ -704,12 +731,12 @@ __device__ __forceinline__ void gemm_f16_primed(Acc &acc, HRing<DIST> &R, const 
     if (F) __builtin_amdgcn_s_setprio(0);
 }
 
-template <int NKS, int DIST = H_DIST>
+template <int NKS, int DIST = H_DIST, int NP = 2>
 __device__ __forceinline__ void gemm_f16(Acc &acc, const float *__restrict__ wp, const _Float16 *pb0,
                                          const _Float16 *pb1, Fair *F = nullptr) {
-    HRing<DIST> R;
-    hring_prime<DIST, NKS>(R, wp);
-    gemm_f16_primed<NKS, DIST>(acc, R, wp, pb0, pb1, F);
+    HRing<DIST, NP> R;
+    hring_prime<DIST, NKS, NP>(R, wp);
+    gemm_f16_primed<NKS, DIST, NP>(acc, R, wp, pb0, pb1, F);
 }
 
 // 4 (or 8) fp32 values -> scaled fp16 parts written to P0 / P1 at half offset `off`
@@ -765,7 +792,27 @@ __device__ __forceinline__ void put_split4_pair(_Float16 *Pl, int off, const f4 
     *reinterpret_cast<u4 *>(Pl + off) = u4{w0[0], w1[0], w0[1], w1[1]};
 #endif
 }
-template <bool RELU = true>
+// The single-part publish (PREC 1): relu(acc) * 2^e_col rounded ONCE to fp16 (v_cvt_pk_f16_f32,
+// RNE), no residual, P0 only.  The store keeps the pair store's shape with the row-tile pair
+// (r, r + 1) in the place of the part pair: lanes g and g ^ 1 hold rows 4g .. 4g + 3 of one column
+// in both row tiles; after one v_permlane16_swap per dword the even lane holds row tile r's 8-row
+// chunk (16 B, k order) and the odd lane row tile r + 1's, each stored with ONE ds_write_b128 in
+// P0.  Per store instruction a lane row's 16 columns land at the pitch / swizzle addresses of
+// f16x3's publish (eight consecutive lanes, eight distinct bank quads), and the image keeps the
+// layout the B reads are conflict-free on; 8 stores per lane and layer where f16x3 issues 16.
+__device__ __forceinline__ void put_f16x4_pair(_Float16 *q, int off, const f4 &va, const f4 &vb, float s) {
+    const f2 a0 = {va.x * s, va.y * s}, a1 = {va.z * s, va.w * s};
+    const f2 b0 = {vb.x * s, vb.y * s}, b1 = {vb.z * s, vb.w * s};
+    const u2 pa = {__builtin_bit_cast(unsigned, __builtin_convertvector(a0, h2)),
+                   __builtin_bit_cast(unsigned, __builtin_convertvector(a1, h2))};
+    const u2 pb = {__builtin_bit_cast(unsigned, __builtin_convertvector(b0, h2)),
+                   __builtin_bit_cast(unsigned, __builtin_convertvector(b1, h2))};
+    const auto w0 = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
+    const auto w1 = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    *reinterpret_cast<u4 *>(q + off) = u4{w0[0], w1[0], w0[1], w1[1]};
+}
+template <bool RELU = true, int NP = 2>
 __device__ __forceinline__ void relu_store_split(const Acc &acc, _Float16 *P0, _Float16 *P1,
                                                  const float *cmax, int *ecol, int wave, int lane,
                                                  int (&e_col)[CT]) {
@@ -774,7 +821,7 @@ __device__ __forceinline__ void relu_store_split(const Acc &acc, _Float16 *P0, _
     // store bases of row tiles r = 0 and 1 (r + 2: +32 halves, the swizzle only XORs the low two
     // chunk bits; column tile c: +16 ROWH, the swizzle depends on column bits 2-3 only), so the
     // 16 stores take constant ds_write offsets
-    _Float16 *Pl = (g & 1) ? P1 : P0;
+    _Float16 *Pl = (NP > 1 && (g & 1)) ? P1 : P0;
     const int kb = 16 * RTW * wave + 4 * (g & ~1);
     _Float16 *q0 = Pl + cl * ROWH + swz(cl, kb), *q1 = Pl + cl * ROWH + swz(cl, kb + 16);
     // every column exponent first: a wave's LDS operations complete in order, so a cmax read
@@ -799,6 +846,16 @@ __device__ __forceinline__ void relu_store_split(const Acc &acc, _Float16 *P0, _
     for (int c = 0; c < CT; ++c) {
         const int col = 16 * c + cl;
         const float sc = __builtin_ldexpf(1.f, e_col[c]);
+        if constexpr (NP == 1) {
+            // even lane rows store row tile 2j's chunk (q0), odd ones row tile 2j + 1's (q1)
+            static_assert(RTW % 2 == 0, "row-tile pairs");
+#pragma unroll
+            for (int j = 0; j < RTW / 2; ++j) {
+                const f4 va = RELU ? relu4(acc[2 * j][c]) : acc[2 * j][c];
+                const f4 vb = RELU ? relu4(acc[2 * j + 1][c]) : acc[2 * j + 1][c];
+                put_f16x4_pair((g & 1) ? q1 : q0, c * 16 * ROWH + j * 32, va, vb, sc);
+            }
+        } else {
 #pragma unroll
         for (int r = 0; r < RTW; ++r) {
             const f4 v = acc[r][c];
@@ -808,6 +865,7 @@ __device__ __forceinline__ void relu_store_split(const Acc &acc, _Float16 *P0, _
             const f4 o = RELU ? relu4(v) : v;
 #endif
             put_split4_pair((r & 1) ? q1 : q0, c * 16 * ROWH + (r >> 1) * 32, o, sc);
+        }
         }
     }
 }
@@ -997,14 +1055,16 @@ __device__ __forceinline__ void add_stage(Acc &x, const float *stage, int wave, 
 // R: a ring primed (hring_prime) on this layer's weights, or nullptr (PREC 3 only).
 // OWN (PREC 3, the input image written by the wave's last publish): the column exponents come from
 // that publish's registers (g.ecl) instead of LDS, so the accumulator scaling does not wait on a read.
-template <int PREC, int NK, int DIST = H_DIST, bool OWN = false>
+// NP (PREC 3 / 1): the parts of this layer's weights and input image; PREC 1 runs its 512-wide
+// layers with 1 and lin_in with 2 (g.ws_off is the offset in the mode's 512-wide layers).
+template <int PREC, int NK, int DIST = H_DIST, bool OWN = false, int NP = nparts(PREC)>
 __device__ __forceinline__ void layer_gemm(Acc &acc, const float *layer_base, GemmCtx &g, int hidx,
-                                           HRing<DIST> *R = nullptr) {
+                                           HRing<DIST, NP> *R = nullptr) {
     PT(g, 3);
     PT_COUNT(g, 5);
     if constexpr (PREC == 0) {
         gemm<NK>(acc, layer_base + g.wl_off, g.inb4);
-    } else if constexpr (PREC == 3) {
+    } else if constexpr (is_h(PREC)) {
         // the accumulators run in the products' scale 2^(eW + e_col): exact for powers of
         // two, so the fp32 rounding sequence is that of the unscaled sum
         const int cl = opaque_lane(g.lane) & 15;
@@ -1023,8 +1083,10 @@ __device__ __forceinline__ void layer_gemm(Acc &acc, const float *layer_base, Ge
                 acc[r][c] *= sa[c];
             }
         Fair *F = g.fair.prog ? &g.fair : nullptr;
-        if (R) gemm_f16_primed<NK / 2, DIST>(acc, *R, layer_base + opaque_lane((int)g.ws_off), g.pb0, g.pb1, F);
-        else gemm_f16<NK / 2, DIST>(acc, layer_base + opaque_lane((int)g.ws_off), g.pb0, g.pb1, F);
+        // this wave's first row tile + this lane, in the layer's own part count
+        const int wso = NP == nparts(PREC) ? (int)g.ws_off : RTW * g.wave * srt_h_floats(NP) + g.lane * 4;
+        if (R) gemm_f16_primed<NK / 2, DIST, NP>(acc, *R, layer_base + opaque_lane(wso), g.pb0, g.pb1, F);
+        else gemm_f16<NK / 2, DIST, NP>(acc, layer_base + opaque_lane(wso), g.pb0, g.pb1, F);
 #pragma unroll
         for (int r = 0; r < RTW; ++r)
 #pragma unroll
@@ -1134,6 +1196,9 @@ __device__ __forceinline__ void march_epilogue(const Args &a, int64_t b, const f
 template <int PREC, bool PZ, bool MARCH>
 __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     constexpr int KD = H_DIST;   // weight ring distance
+    constexpr bool HP = is_h(PREC);      // a scaled-fp16 mode: f16x3 (3) or f16 (1)
+    constexpr int NP = nparts(PREC);     // parts of the 512-wide layers' weights and of the publish
+    static_assert(PREC != 1 || PZ, "PREC 1 is built for the projected-latent path only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *inbuf = smem;                   // COLS x LDS_LD
     const int tid = threadIdx.x;
@@ -1145,7 +1210,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
 
     // per-lane fragment bases
     const int64_t wl_off = (int64_t)(RTW * wave) * 256 + lane * 4;         // f32 fragments
-    const int64_t ws_off = (int64_t)(RTW * wave) * (PREC == 3 ? SRT16_FLOATS : SRT_FLOATS) + lane * 4;
+    const int64_t ws_off = (int64_t)(RTW * wave) * (HP ? srt_h_floats(NP) : SRT_FLOATS) + lane * 4;
     const float *inb = inbuf + cl * LDS_LD + 4 * g;     // B (f32): column 16c + cl, k 16kb + 4g
     GemmCtx gc;
     gc.wl_off = wl_off;
@@ -1153,15 +1218,18 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     gc.inb4 = inb;
     gc.inbw = inbuf + (16 * (wave % CT) + cl) * LDS_LD + 8 * g + 4 * (wave / CT);
     gc.stg = inbuf + COLS * LDS_LD;
-    // PREC 3 LDS: P0 | P1 | gtab | cmax | ecol; else: inbuf (fp32) | staging | gtab
+    // PREC 3 / 1 LDS: P0 | P1 | gtab | cmax | ecol; else: inbuf (fp32) | staging | gtab
+    // (PREC 1: the 512-wide layers' image is P0 alone; P1 holds lin_in's second feature part.  The
+    // image region is sized by the fp32 stage of the projected latent that aliases it, 132,096 B of
+    // P0 + P1's 135,168 B, so the map and the launch's LDS size are PREC 3's.)
     _Float16 *P0 = reinterpret_cast<_Float16 *>(smem);
     _Float16 *P1 = P0 + PART_HALVES;
-    float *gtab = PREC == 3 ? reinterpret_cast<float *>(P1 + PART_HALVES) : gc.stg + 2 * STG_FLOATS;
+    float *gtab = HP ? reinterpret_cast<float *>(P1 + PART_HALVES) : gc.stg + 2 * STG_FLOATS;
     float *cmax = gtab + COLS * 8;           // PREC 3: per-column partial maxima (64 x 8)
     int *ecol = reinterpret_cast<int *>(cmax + COLS * 8);
     // PE freqs [0, 16) / phases [16, 32) of the pack header, in LDS: the feature loop indexes
     // them per lane, and vector global loads there put a memory latency in every iteration
-    float *petab = PREC == 3 ? reinterpret_cast<float *>(ecol + COLS) : gtab + COLS * 8;
+    float *petab = HP ? reinterpret_cast<float *>(ecol + COLS) : gtab + COLS * 8;
     // (the one-time LDS fills below are whole-wave writes -- lanes 32 apart store the same value --
     // rather than `if (tid < 32)` branches: no divergent region for a misplaced spill, claim_one)
     if (wave == 0) petab[lane & 31] = a.packed[lane & 31];   // visible after the first barrier of a tile
@@ -1174,7 +1242,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     gc.fair.wave = wave;
     gc.fair.it = 0;
     gc.fair.mate = 0;
-    if constexpr (PREC == 3) {
+    if constexpr (HP) {
         gc.fair.prog = reinterpret_cast<int *>(petab + 40);   // petab + 32 / 33: s_next, + 64: hpart
         if (wave == 0) gc.fair.prog[lane & (WAVES - 1)] = 0;   // visible after the first barrier
     }
@@ -1202,7 +1270,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     // early start the publish VALU under their SIMD-mate's MFMAs.
     auto pre_publish_sync = [&]() {
 #ifndef PNR_GEMM_ONLY
-        if constexpr (PREC != 3)
+        if constexpr (!HP)
 #endif
             lds_barrier();
     };
@@ -1223,7 +1291,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             return;
         }
 #endif
-        if constexpr (PREC == 3) {
+        if constexpr (HP) {
             // (phase-timing slots 17, 13-15, 16: glue split into the ring prime / bias loads
             // before the publish, colmax VALU, its barrier, the split, the closing barrier)
             PT(gc, 17);
@@ -1231,7 +1299,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             PT(gc, 13);
             lds_barrier();
             PT(gc, 14);
-            relu_store_split(acc, P0, P1, cmax, ecol, wave, lane, gc.ecl);
+            relu_store_split<true, NP>(acc, P0, P1, cmax, ecol, wave, lane, gc.ecl);
             PT(gc, 15);
         } else {
             store_relu(acc, inbuf, wave, lane);
@@ -1258,7 +1326,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     // near / far.  (Deferring a ray's epilogue into the next tile, under the SIMD-mate's MFMAs,
     // was measured: the double buffers and the call inside the GEMM region cost more in spills
     // than it hid.)
-    float *mreg = PREC == 3 ? hpart + 2048 : petab + 36;
+    float *mreg = HP ? hpart + 2048 : petab + 36;
     float *mscr = mreg + MARCH_BUF_FLOATS;
     float *mnf = mscr + 384;
     const int kpt = MARCH ? march_cfg(a)->kpt : 1;   // tiles per ray and pass when marching
@@ -1404,7 +1472,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                         *reinterpret_cast<f4 *>(sv_f + (v * P + p_raw) * 64 + FPT * qt + 4 * i) =
                             f4{fv[4 * i], fv[4 * i + 1], fv[4 * i + 2], fv[4 * i + 3]};
                 }
-                if constexpr (PREC == 3) {
+                if constexpr (HP) {
                     // column max over its WAVES feature threads (adjacent lanes), scale, split
                     float m = 0.f;
 #pragma unroll
@@ -1463,7 +1531,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             PT(gc, 0);
             // ---- lin_in ---------------------------------------------------------------
             add_bias(x, bias, wave, lane, false);
-            layer_gemm<PREC, NKB_IN, KD>(x, PK() + L.off_lin_in, gc, 0);
+            layer_gemm<PREC, NKB_IN, KD, false, 2>(x, PK() + L.off_lin_in, gc, 0);   // two-part in PREC 1 too
             // ---- blocks before the combine layer: x += lin_z(z); x = block(x) ------
             for (int blk = 0; blk < L.ncomb; ++blk) {
                 const int lz = layer_index(blk, 0, L.ncomb);
@@ -1508,12 +1576,12 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                         for (int q = 0; q < 4; ++q)
                             zz[q] = add_rn(add_rn(add_rn(mul_rn(c0[q], tw.x), mul_rn(c1[q], tw.y)),
                                                   mul_rn(c2[q], tw.z)), mul_rn(c3[q], tw.w));
-                        if constexpr (PREC == 3) zh[half] = zz;
+                        if constexpr (HP) zh[half] = zz;
                         else *reinterpret_cast<f4 *>(inbuf + cj * LDS_LD + ch) = zz;
                         if (a.save && blk == 0 && tile * COLS + cj < P)
                             *reinterpret_cast<f4 *>(sv_z + (v * P + tile * COLS + cj) * H + ch) = zz;
                     }
-                    if constexpr (PREC == 3) {
+                    if constexpr (HP) {
                         // column max over the wave (all 512 channels), scale, split
                         float m = 0.f;
 #pragma unroll
@@ -1534,29 +1602,29 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                 layer_gemm<PREC, NKB, KD>(x, PK() + L.off_l512 + (int64_t)lz * L.layer_floats, gc, 1 + lz);
                 pre_publish_sync();
                 }
-                HRing<KD> R0;   // fc_0's ring, primed before or during the publish (PREC 3)
+                HRing<KD, NP> R0;   // fc_0's ring, primed before or during the publish (PREC 3)
                 const float *w0p = PK() + L.off_l512 + (int64_t)(lz + 1) * L.layer_floats;
-                if constexpr (PREC == 3) hring_prime(R0, w0p + opaque_lane((int)gc.ws_off));
+                if constexpr (HP) hring_prime(R0, w0p + opaque_lane((int)gc.ws_off));
                 f4 nb0[RTW];   // fc_0's bias rows, loaded before the publish too
                 load_bias(nb0, bias + (2 + lz) * H, wave, lane);
                 publish_relu(x, tile, blk, v * P);
                 lds_barrier();
                 PT(gc, 16);
                 set_bias(h, nb0, false);
-                layer_gemm<PREC, NKB, KD, PREC == 3>(h, PK() + L.off_l512 + (int64_t)(lz + 1) * L.layer_floats, gc, 2 + lz,
-                                          PREC == 3 ? &R0 : nullptr);
+                layer_gemm<PREC, NKB, KD, HP>(h, PK() + L.off_l512 + (int64_t)(lz + 1) * L.layer_floats, gc, 2 + lz,
+                                          HP ? &R0 : nullptr);
                 pre_publish_sync();
-                HRing<KD> R1;   // fc_1's
+                HRing<KD, NP> R1;   // fc_1's
                 const float *w1p = PK() + L.off_l512 + (int64_t)(lz + 2) * L.layer_floats;
-                if constexpr (PREC == 3) hring_prime(R1, w1p + opaque_lane((int)gc.ws_off));
+                if constexpr (HP) hring_prime(R1, w1p + opaque_lane((int)gc.ws_off));
                 f4 nb1[RTW];
                 load_bias(nb1, bias + (3 + lz) * H, wave, lane);
                 publish_relu(h, tile, L.n_blocks + blk, v * P);
                 lds_barrier();
                 PT(gc, 16);
                 set_bias(x, nb1, true);
-                layer_gemm<PREC, NKB, KD, PREC == 3>(x, PK() + L.off_l512 + (int64_t)(lz + 2) * L.layer_floats, gc, 3 + lz,
-                                          PREC == 3 ? &R1 : nullptr);
+                layer_gemm<PREC, NKB, KD, HP>(x, PK() + L.off_l512 + (int64_t)(lz + 2) * L.layer_floats, gc, 3 + lz,
+                                          HP ? &R1 : nullptr);
             }
             // ---- multi-view mean (combine_interleaved: sum over views, then / NS) --
             if (a.ns > 1) {
@@ -1591,34 +1659,34 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
         for (int blk = L.ncomb; blk < L.n_blocks; ++blk) {
             const int l0 = layer_index(blk, 1, L.ncomb);
             pre_publish_sync();
-            HRing<KD> R0;
+            HRing<KD, NP> R0;
             const float *w0p = PK() + L.off_l512 + (int64_t)l0 * L.layer_floats;
-            if constexpr (PREC == 3) hring_prime(R0, w0p + opaque_lane((int)gc.ws_off));
+            if constexpr (HP) hring_prime(R0, w0p + opaque_lane((int)gc.ws_off));
             f4 nb0[RTW];
             load_bias(nb0, bias + (1 + l0) * H, wave, lane);
             publish_relu(x, tile, blk, 0);
             lds_barrier();
             PT(gc, 16);
             set_bias(h, nb0, false);
-            layer_gemm<PREC, NKB, KD, PREC == 3>(h, PK() + L.off_l512 + (int64_t)l0 * L.layer_floats, gc, 1 + l0,
-                                      PREC == 3 ? &R0 : nullptr);
+            layer_gemm<PREC, NKB, KD, HP>(h, PK() + L.off_l512 + (int64_t)l0 * L.layer_floats, gc, 1 + l0,
+                                      HP ? &R0 : nullptr);
             pre_publish_sync();
-            HRing<KD> R1;
+            HRing<KD, NP> R1;
             const float *w1p = PK() + L.off_l512 + (int64_t)(l0 + 1) * L.layer_floats;
-            if constexpr (PREC == 3) hring_prime(R1, w1p + opaque_lane((int)gc.ws_off));
+            if constexpr (HP) hring_prime(R1, w1p + opaque_lane((int)gc.ws_off));
             f4 nb1[RTW];
             load_bias(nb1, bias + (2 + l0) * H, wave, lane);
             publish_relu(h, tile, L.n_blocks + blk, 0);
             lds_barrier();
             PT(gc, 16);
             set_bias(x, nb1, true);
-            layer_gemm<PREC, NKB, KD, PREC == 3>(x, PK() + L.off_l512 + (int64_t)(l0 + 1) * L.layer_floats, gc, 2 + l0,
-                                      PREC == 3 ? &R1 : nullptr);
+            layer_gemm<PREC, NKB, KD, HP>(x, PK() + L.off_l512 + (int64_t)(l0 + 1) * L.layer_floats, gc, 2 + l0,
+                                      HP ? &R1 : nullptr);
         }
         // ---- lin_out(relu(x)) + head [sigmoid(rgb), relu(sigma)]: wave w < CT -> columns 16w..
         if (wave == 0) *s_next = s_in + 1 < upt ? (int)tile + 1 : grab();   // read after the closing barrier
         pre_publish_sync();
-        if constexpr (PREC == 3) {
+        if constexpr (HP) {
             // no publish: the head reads relu(x) from the accumulators (below); only the
             // activation save of lin_out's input remains
             if (a.save) {
@@ -1634,7 +1702,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
 #ifdef PNR_GEMM_ONLY
         if (0)
 #endif
-        if (PREC == 3) {
+        if (HP) {
             // fp32 head straight from the accumulators (resnetfc.py:184 lin_out on relu(x)):
             // lane (g, cl) holds rows 16 (RTW wave + r) + 4 g + i of column 16 c + cl; it sums
             // W_out^T (fp32, [channel][output] at off_out32) times relu(x) over its 16 rows, then
@@ -1666,7 +1734,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                 for (int j = 0; j < 4; ++j) o[c][j] = rows_sum(o[c][j]);
             const f4 mine = g4 == 0 ? o[0] : g4 == 1 ? o[1] : g4 == 2 ? o[2] : o[3];
             *reinterpret_cast<f4 *>(hpart + (wave * COLS + 16 * g4 + c16) * 4) = mine;
-        } else if (PREC != 3 && wave < CT) {   // wave-uniform: the first CT waves own one column tile each
+        } else if (!HP && wave < CT) {   // wave-uniform: the first CT waves own one column tile each
             const float *wo = PK() + L.off_lin_out + lane * 4;
             const float *bi = inbuf + (16 * wave + cl) * LDS_LD + 4 * g;
             f4 o0 = *reinterpret_cast<const f4 *>(bias + (1 + L.n_l512) * H + 4 * g);
@@ -1697,7 +1765,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
         PT(gc, 4);
         PT_COUNT(gc, 6);
         lds_barrier();   // s_next and the head partials written
-        if (PREC == 3 && wave < CT) {   // [sigmoid(rgb), relu(sigma)] of column tile `wave`
+        if (HP && wave < CT) {   // [sigmoid(rgb), relu(sigma)] of column tile `wave`
             const int ln = opaque_lane(lane), gg = ln >> 4, cc = ln & 15;
             const int col = 16 * wave + cc;
             f4 o = *reinterpret_cast<const f4 *>(hpart + col * 4);
@@ -2060,10 +2128,10 @@ int mlp_check_desc(const pnr_mlp_desc &d) {
     if (d.d_in != 3 + 3 * d.pe_n + 3)
         return fail(PNR_ERR_UNSUPPORTED, "d_in must be 3 + 3*pe_n + 3 (xyz PE + raw viewdirs); got %d", d.d_in);
     if (d.d_in > 16 * mlpk::NKB_IN) return fail(PNR_ERR_UNSUPPORTED, "d_in <= 64");
-    if (d.precision != PNR_PREC_F32 && d.precision != PNR_PREC_F16X3 && d.precision != PNR_PREC_BF16X6 &&
-        d.precision != PNR_PREC_BF16X9)
-        return fail(PNR_ERR_UNSUPPORTED, "precision must be 0 (f32), 3 (scaled f16) or 6 / 9 (split bf16); got %d",
-                    d.precision);
+    if (d.precision != PNR_PREC_F32 && d.precision != PNR_PREC_F16 && d.precision != PNR_PREC_F16X3 &&
+        d.precision != PNR_PREC_BF16X6 && d.precision != PNR_PREC_BF16X9)
+        return fail(PNR_ERR_UNSUPPORTED, "precision must be 0 (f32), 1 (f16, one product), 3 (f16x3) or 6 / 9 "
+                    "(split bf16); got %d", d.precision);
     return PNR_OK;
 }
 
@@ -2102,7 +2170,7 @@ int mlp_pack(const pnr_mlp_weights &w, void *packed, size_t bytes, hipStream_t s
                        static_cast<float *>(packed));
     if (!launch_ok("mlp_pack")) return PNR_ERR_HIP;
     const int64_t n = (int64_t)(mlpk::KS32_IN + L.n_l512 * mlpk::KS32) * mlpk::NRT * 64;
-    if (L.prec == PNR_PREC_F16X3) {
+    if (mlpk::is_h(L.prec)) {
         float *hdr = static_cast<float *>(packed);
         if (hipMemsetAsync(hdr + mlpk::HDR_ESCALE, 0, sizeof(float) * (1 + L.n_l512), st) != hipSuccess)
             return fail(PNR_ERR_HIP, "mlp_pack: hipMemsetAsync failed");
@@ -2213,6 +2281,9 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *pac
                      int64_t n_points, float *out, float *xsum_ws, hipStream_t st, float *save,
                      const float *proj, const MarchCfg *march) {
     if (n_points == 0) return PNR_OK;
+    if (d.precision == PNR_PREC_F16 && (!proj || save))
+        return fail(PNR_ERR_UNSUPPORTED, "precision 1 (f16) is inference only on the projected-latent path: it "
+                    "needs the latent projection and takes no activation save; use precision 3 (f16x3)");
     if (proj && save) return fail(PNR_ERR_UNSUPPORTED, "the activation save (training) needs the latent gather path");
     if (march && (!rays || save || (march->kpt != 1 && march->kpt != 2) || K != mlpk::COLS * march->kpt ||
                   n_points % K != 0 || (march->kf > 0 && (K > 64 || march->n_sort > 128 || K + march->kf > march->n_sort))))
@@ -2246,10 +2317,11 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *pac
     a.tile_ctr = reinterpret_cast<int *>(xsum_ws + (size_t)cus * 2 * mlpk::COLS * mlpk::H);
     if (hipMemsetAsync(a.tile_ctr, 0, 512, st) != hipSuccess) return fail(PNR_ERR_HIP, "point_mlp: hipMemsetAsync failed");
     const int64_t grid = a.n_tiles < cus ? a.n_tiles : cus;
-    // PREC 3: split image P0 + P1, gather records, column maxima, exponents, PE table, next tile
+    // PREC 3 / 1: split image P0 + P1 (PREC 1: P0 and, for lin_in, P1; sized by the fp32 stage that
+    //         aliases them), gather records, column maxima, exponents, PE table, next tile
     //         = 143,760 B; else: fp32 activations + staging ring + gather records + PE table +
     //         next tile = 158,864 B
-    const size_t lds = (d.precision == PNR_PREC_F16X3
+    const size_t lds = (mlpk::is_h(d.precision)
         ? 2 * sizeof(_Float16) * mlpk::PART_HALVES + sizeof(float) * (2 * mlpk::COLS * 8 + mlpk::COLS + 64 + 2048)
         : sizeof(float) * ((size_t)mlpk::COLS * mlpk::LDS_LD + 2 * mlpk::STG_FLOATS + mlpk::COLS * 8 + 32 + 4)
         ) + (march ? sizeof(float) * MARCH_LDS_FLOATS : 0);   // + the fused march region
@@ -2261,6 +2333,10 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *pac
         else hipLaunchKernelGGL((mlpk::k_point_mlp<P, false, false>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);     \
     } while (0)
     switch (d.precision) {
+    case PNR_PREC_F16:   // PZ only (checked above)
+        if (march) hipLaunchKernelGGL((mlpk::k_point_mlp<1, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
+        else hipLaunchKernelGGL((mlpk::k_point_mlp<1, true, false>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
+        break;
     case PNR_PREC_F16X3: PNR_LAUNCH_MLP(3); break;
     case PNR_PREC_BF16X6: PNR_LAUNCH_MLP(6); break;
     case PNR_PREC_BF16X9: PNR_LAUNCH_MLP(9); break;

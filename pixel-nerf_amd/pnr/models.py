@@ -43,7 +43,20 @@ __all__ = ["PositionalEncoding", "ResnetBlockFC", "ResnetFC", "PixelNeRFNet", "m
 #   "f16x3"  power-of-two scaled operands (per layer / per activation column), each
 #            split into two fp16 parts; 3 exact products on v_mfma_f32_16x16x32_f16
 #            (error at the fp32 level, tools/precision_study.py)
-PRECISIONS = {"fp32": 0, "f16x3": 3, "bf16x6": 6, "bf16x9": 9}
+# and one mode that trades accuracy for time, INFERENCE ONLY:
+#   "f16"    f16x3's power-of-two scaling, but every operand of the 512 -> 512 layers is
+#            rounded once to fp16: one product per k-step, a single-part weight stream of half
+#            the bytes.  lin_in, the projected lin_z contribution, the view mean and the head
+#            stay as in f16x3.  max |d rgb| 6e-4 per point / 4e-4 per ray (an 8-bit step is
+#            3.9e-3; DESIGN.md §4, tests/f16_emul.py).  It needs the projected-latent path
+#            (use_latent_proj and lin_z layers) and refuses every training / autograd path.
+PRECISIONS = {"fp32": 0, "f16": 1, "f16x3": 3, "bf16x6": 6, "bf16x9": 9}
+
+
+def f16_refusal(what):
+    """The error of a path that mlp_precision = "f16" does not serve (raised before any device
+    work)."""
+    return NotImplementedError('pnr: mlp_precision "f16" is inference only; use f16x3 (%s)' % what)
 
 
 def _own_params(m):
@@ -513,7 +526,18 @@ class PixelNeRFNet(nn.Module):
         return any(p.requires_grad for p in module_params(self, skip="encoder")) \
             or (lat.requires_grad and not self.stop_encoder_grad)
 
+    def _check_f16(self):
+        """mlp_precision = "f16" runs the projected-latent kernels only (PNR_PREC_F16)."""
+        if self.mlp_precision != "f16":
+            return
+        if not self.use_latent_proj:
+            raise f16_refusal("use_latent_proj = False: the f16 kernels run on the projected latent only")
+        for mlp in (self.mlp_coarse, self.mlp_fine):
+            if mlp is not None and len(getattr(mlp, "lin_z", [])) == 0:
+                raise f16_refusal("an MLP without lin_z layers has no projected latent")
+
     def _require_hip(self):
+        self._check_f16()
         r = self.hip_unsupported_reason()
         if r:
             raise NotImplementedError("pnr: " + r)
@@ -536,6 +560,7 @@ class PixelNeRFNet(nn.Module):
         mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
         if self.mlp_precision not in PRECISIONS:
             raise ValueError("mlp_precision must be one of %s" % sorted(PRECISIONS))
+        self._check_f16()
         return mlp.packed(self.code, self.mlp_precision)
 
     def hip_proj(self, coarse, scene=None):
@@ -590,6 +615,8 @@ class PixelNeRFNet(nn.Module):
     def _forward_points_grad(self, xyz, coarse, viewdirs):
         """The point query with its autograd graph (see forward): one training-forward sample per
         point, rays [xyz, viewdirs, 0, 0] at z = 0."""
+        if self.mlp_precision == "f16":
+            raise f16_refusal("a point query under autograd")
         from .ops import _dev
         from .train import RenderPoints, mlp_params
 

@@ -250,6 +250,10 @@ class NeRFRenderer(torch.nn.Module):
         noise, u_fine, u_fine_jit, n_depth, fine noise."""
         from .train import Composite, FinePass, RenderPoints, mlp_params
 
+        if net.mlp_precision == "f16":
+            from .models import f16_refusal
+
+            raise f16_refusal("a render under autograd or with training-mode sigma noise")
         r = net.hip_unsupported_reason()
         if r:
             raise NotImplementedError("pnr: " + r)

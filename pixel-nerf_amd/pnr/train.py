@@ -306,6 +306,10 @@ class RenderPoints(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, coarse, rays, z, latent_cl, *params):
+        if net.mlp_precision == "f16":
+            from .models import f16_refusal
+
+            raise f16_refusal("train.RenderPoints, the training forward")
         mlp = net.mlp_coarse if (coarse or net.mlp_fine is None) else net.mlp_fine
         desc, packed = mlp.packed(net.code, net.mlp_precision)
         sc = net.hip_scene()

@@ -29,7 +29,7 @@ import torch  # noqa: E402
 from pnr import evaluate, util  # noqa: E402
 from pnr.conf import parse_file  # noqa: E402
 from pnr.data import get_split_dataset  # noqa: E402
-from pnr.models import make_model  # noqa: E402
+from pnr.models import PRECISIONS, make_model  # noqa: E402
 from pnr.renderer import NeRFRenderer  # noqa: E402
 
 CHUNK = 65536   # eval.py:99
@@ -76,6 +76,9 @@ def main(argv=None):
     ap.add_argument("--compare", action="store_true", help="render and score the non-source views")
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
+    ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
+                    help="arithmetic of the fused MLP (pnr.models.PRECISIONS); f16 trades accuracy below an "
+                         "8-bit step for time")
     args = ap.parse_args(argv)
     args.resume = True
 
@@ -84,6 +87,7 @@ def main(argv=None):
     conf = parse_file(args.conf)
     dset = get_split_dataset(args.dataset_format, args.datadir, want_split=args.split, training=False)
     net = make_model(conf["model"]).to(device=device).load_weights(args)
+    net.mlp_precision = args.precision
     net.eval()
     renderer = NeRFRenderer.from_conf(conf["renderer"], lindisp=dset.lindisp,
                                       eval_batch_size=args.ray_batch_size).to(device)

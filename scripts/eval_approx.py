@@ -20,7 +20,7 @@ import torch  # noqa: E402
 from pnr import evaluate  # noqa: E402
 from pnr.conf import parse_file  # noqa: E402
 from pnr.data import get_split_dataset  # noqa: E402
-from pnr.models import make_model  # noqa: E402
+from pnr.models import PRECISIONS, make_model  # noqa: E402
 from pnr.renderer import NeRFRenderer  # noqa: E402
 
 
@@ -38,12 +38,16 @@ def main():
     ap.add_argument("--coarse", action="store_true")
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
+    ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
+                    help="arithmetic of the fused MLP (pnr.models.PRECISIONS); f16 trades accuracy below an "
+                         "8-bit step for time")
     args = ap.parse_args()
     args.resume = True
 
     conf = parse_file(args.conf)
     dev = torch.device("cuda", args.gpu_id)
     net = make_model(conf["model"]).to(device=dev)
+    net.mlp_precision = args.precision
     net.load_weights(args)
     dset = get_split_dataset(args.dataset_format, args.datadir, want_split=args.split, training=False)
     renderer = NeRFRenderer.from_conf(conf["renderer"], eval_batch_size=args.ray_batch_size).to(device=dev)

@@ -26,7 +26,7 @@ import torch  # noqa: E402
 from pnr import util, video  # noqa: E402
 from pnr.conf import parse_file  # noqa: E402
 from pnr.data import get_split_dataset  # noqa: E402
-from pnr.models import make_model  # noqa: E402
+from pnr.models import PRECISIONS, make_model  # noqa: E402
 from pnr.renderer import NeRFRenderer  # noqa: E402
 
 
@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--fps", type=int, default=30)
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
+    ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
+                    help="arithmetic of the fused MLP (pnr.models.PRECISIONS); f16 trades accuracy below an "
+                         "8-bit step for time")
     args = ap.parse_args()
     args.resume = True
 
@@ -69,6 +72,7 @@ def main():
         H, W = Ht, Wt
 
     net = make_model(conf["model"]).to(device=device)
+    net.mlp_precision = args.precision
     net.load_weights(args)
     renderer = NeRFRenderer.from_conf(conf["renderer"], lindisp=dset.lindisp,
                                       eval_batch_size=args.ray_batch_size).to(device=device)
