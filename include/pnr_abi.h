@@ -307,7 +307,8 @@ int pnr_sample_fine(const float *rays, int64_t n_rays, int32_t n_coarse,
 /* Replaces: NeRFRenderer.composite's alpha compositing (nerf.py:176-249).
  * z (n_rays, K), raw (n_rays, K, 4) = model output [r, g, b, sigma];
  * weights (n_rays, K) may be NULL; rgb (n_rays, 3); depth (n_rays).
- * raw must be 16-byte aligned (PNR_ERR_INVALID otherwise); z and weights need only float
+ * Any k >= 1 is supported (k <= 256 runs the register-resident kernels, larger k the chunked
+ * one).  raw must be 16-byte aligned (PNR_ERR_INVALID otherwise); z and weights need only float
  * alignment. */
 int pnr_composite(const float *z, const float *raw, const float *rays, int64_t n_rays,
                   int32_t k, int32_t white_bkgd, float *weights, float *rgb, float *depth,

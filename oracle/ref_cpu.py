@@ -19,6 +19,7 @@ Functions and the reference lines they restate:
 * ``render``             nerf.py:251-303 (+ _format_outputs 305-316)
 * ``encode_buffers``     models.py:89-141 (post-CNN part: poses/focal/c)
 * ``pixelnerf_forward``  models.py:146-266
+* ``pixelnerf_input_stage`` models.py:156-221 (the part of it before the ResnetFC)
 * ``positional_encoding`` code.py:30-42
 * ``index_latent``       encoder.py:80-109 (grid_sample, align_corners, border)
 * ``resnetfc_forward``   resnetfc.py:132-184 with ResnetBlockFC 53-62
@@ -140,12 +141,12 @@ class Scene:
             poses, focal, width, height, c)
 
 
-def pixelnerf_forward(sd, scene, xyz, coarse=True, viewdirs=None, d_latent=512,
-                      n_blocks=5, combine_layer=3, has_fine=True, relu=None):
-    """models.py:146-266 for the shipped conf (use_xyz, normalize_z, use_code,
-    use_viewdirs, use_code_viewdirs=False, no global encoder).  MLP rows before
-    combine_layer are (object, view, point), after it (object, point); ``relu`` as
-    resnetfc_forward."""
+def pixelnerf_input_stage(sd, scene, xyz, viewdirs, d_latent=512):
+    """The input stage of models.py:146-266 (lines 156-221): world -> camera transform,
+    positional encoding of the rotated point, rotated view direction, projection and the
+    bilinear latent gather.  xyz / viewdirs (SB, B, 3).  Returns (latent_rows
+    (SB*NS*B, d_latent), z_feature (SB*NS*B, 42)), rows (object, view, point): the two
+    halves of the ResnetFC input."""
     SB, B, _ = xyz.shape
     NS = scene.ns
     poses = scene.poses
@@ -163,6 +164,18 @@ def pixelnerf_forward(sd, scene, xyz, coarse=True, viewdirs=None, d_latent=512,
     uv += repeat_interleave(scene.c.unsqueeze(1), NS if scene.c.shape[0] > 1 else 1)
     latent = index_latent(scene.latent, uv, scene.image_shape)
     latent = latent.transpose(1, 2).reshape(-1, d_latent)
+    return latent, z_feature
+
+
+def pixelnerf_forward(sd, scene, xyz, coarse=True, viewdirs=None, d_latent=512,
+                      n_blocks=5, combine_layer=3, has_fine=True, relu=None):
+    """models.py:146-266 for the shipped conf (use_xyz, normalize_z, use_code,
+    use_viewdirs, use_code_viewdirs=False, no global encoder).  MLP rows before
+    combine_layer are (object, view, point), after it (object, point); ``relu`` as
+    resnetfc_forward."""
+    SB, B, _ = xyz.shape
+    NS = scene.ns
+    latent, z_feature = pixelnerf_input_stage(sd, scene, xyz, viewdirs, d_latent)
     mlp_input = torch.cat((latent, z_feature), dim=-1)
     prefix = "mlp_coarse." if (coarse or not has_fine) else "mlp_fine."
     out = resnetfc_forward(sd, prefix, mlp_input, d_latent, n_blocks, combine_layer, (NS, B), relu=relu)

@@ -244,7 +244,8 @@ int launch_composite(const float *z, const float *raw, const float *rays, int64_
                      int white_bkgd, float *weights, float *rgb, float *depth, hipStream_t st) {
     if (n_rays == 0) return PNR_OK;
     const int nch = (K + 63) / 64;
-    const int64_t grid = (n_rays + 7) / 8;   // one wave per two rays
+    // 4 waves per block: k_composite_c marches two rays per wave, the generic k_composite one
+    const int64_t grid = nch <= 4 ? (n_rays + 7) / 8 : (n_rays + 3) / 4;
     auto kern = nch == 1 ? k_composite_c<1> : nch == 2 ? k_composite_c<2> : nch == 3 ? k_composite_c<3>
               : nch == 4 ? k_composite_c<4> : k_composite;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, z, raw, rays,

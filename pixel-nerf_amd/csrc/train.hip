@@ -15,7 +15,9 @@
 namespace pnr {
 
 // ---------------------------------------------------------------------------
-// composite backward (K <= 64 S; lane l owns samples S l .. S l + S - 1, like the forward)
+// composite backward (K <= 64 S; lane l owns the S consecutive samples S l .. S l + S - 1, so the
+// suffix sum runs inside the lane and then over lanes; the forward's k_composite_c instead uses
+// lane-strided chunks, lane l holding samples 64 i + l)
 //   w_i = a_i T_i,  T_i = prod_{j<i} s_j,  s_j = 1 - a_j + 1e-10,  a = 1 - exp(-delta relu(sigma))
 //   g_i = dL/dw_i = d_rgb . c_i + d_depth z_i (- sum d_rgb if white_bkgd) + d_weights_i
 //   da_i = g_i T_i - (sum_{k>i} g_k w_k) / s_i
@@ -75,16 +77,20 @@ __global__ __launch_bounds__(256) void k_composite_bwd(
         g[i] = valid ? gi : 0.f;
         gw_local += g[i] * w[i];
     }
-    // suffix sums of g w: total - inclusive prefix (over lanes, then inside the lane)
-    float incl = gw_local;
+    // suffix sums of g w (over lanes, then inside the lane), summed from the ray's END: an
+    // inclusive scan over the lanes in reverse order.  The terms decay with the transmittance, and
+    // the sum is divided by s_i below, which is as small as 1e-10 behind an opaque sample: taken as
+    // total - prefix its rounding error (2^-24 of the ray's total) came out 1 / s_i times larger.
+    float incl = __shfl(gw_local, 63 - lane, 64);   // reversed lane r holds lane 63 - r
     incl += dpp_f<0x111>(0.f, incl);
     incl += dpp_f<0x112>(0.f, incl);
     incl += dpp_f<0x114>(0.f, incl);
     incl += dpp_f<0x118>(0.f, incl);
     incl += dpp_f<0x142, 0xa>(0.f, incl);
     incl += dpp_f<0x143, 0xc>(0.f, incl);
-    const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
-    float after = total - incl;   // sum over the lanes after this one
+    // sum over the lanes after this one: lanes l + 1 .. 63 are reversed lanes 0 .. 62 - l
+    float after = __shfl(incl, (62 - lane) & 63, 64);
+    if (lane == 63) after = 0.f;
     float ddel[S];
 #pragma unroll
     for (int i = S - 1; i >= 0; --i) {

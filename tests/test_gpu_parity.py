@@ -89,7 +89,7 @@ def hip_render(cfg, arr, want_weights=True, precision="f16x3", latent_proj=True)
 def test_composite_matches_oracle_random():
     g = torch.Generator().manual_seed(0)
     for B, K, white in [(1, 1, True), (37, 7, False), (300, 64, True), (129, 128, False),
-                        (65, 200, True)]:
+                        (65, 200, True), (65, 300, True)]:
         near, far = 0.3, 4.0
         rays = torch.cat([torch.randn(B, 6, generator=g), torch.full((B, 1), near),
                           torch.full((B, 1), far)], 1)
@@ -120,10 +120,9 @@ def test_composite_empty_batch():
 
 
 def test_composite_unaligned_z_and_weights_through_the_abi():
-    """pnr_composite with z and weights at an odd float offset (a view into a larger buffer): the
-    paired 8-B depth load / weight store is only taken for 8-B-aligned pointers, so
-    the results are bit-identical to the aligned call; raw must be 16-B aligned and is refused
-    otherwise."""
+    """pnr_composite with z and weights at an odd float offset (a view into a larger buffer): z
+    and weights are accessed one float at a time, so a misaligned view gives results bit-identical
+    to the aligned call; only raw needs 16-B alignment and is refused otherwise."""
     import ctypes
 
     from pnr import _lib
