@@ -7,50 +7,9 @@
 #include <cstring>
 
 #include "march_dev.h"
+#include "pnr_launch.h"
 
 namespace pnr {
-
-// launchers (march.hip, mlp.hip)
-int launch_sample_coarse(const float *, int64_t, int, const RngSrc &, int, float *, hipStream_t);
-int launch_sample_fine(const float *, int64_t, int, const float *, const float *, const float *,
-                       int, int, float, const RngSrc &, const RngSrc &, const RngSrc &, int, float *,
-                       hipStream_t, int *origin = nullptr, float *z_new = nullptr);
-int launch_rng_fill(const RngSrc &, int64_t, int, float *, hipStream_t);
-int launch_merge_raw(const int *, const float *, const float *, int64_t, int, int, float *, hipStream_t);
-int launch_gen_rays(const float *, int64_t, int, int, int, float, float, float, float, float, float,
-                    float *, hipStream_t);
-int launch_composite(const float *, const float *, const float *, int64_t, int, int, float *,
-                     float *, float *, hipStream_t);
-size_t mlp_packed_bytes(const pnr_mlp_desc &);
-int mlp_check_desc(const pnr_mlp_desc &);
-int mlp_pack(const pnr_mlp_weights &, void *, size_t, hipStream_t);
-size_t mlp_xsum_bytes(int ns);
-int64_t mlp_save_floats(const pnr_mlp_desc &d, int64_t n_points);
-size_t mlp_packed_t_bytes(const pnr_mlp_desc &);
-int mlp_pack_t(const pnr_mlp_weights &, const void *, void *, size_t, hipStream_t);
-int launch_mlp_bwd(const pnr_mlp_desc &, const void *, const void *, const float *, const float *, const float *,
-                   int64_t, float *, float *, hipStream_t, float *, void *, size_t, int n_views);
-size_t mlp_bwd_workspace_bytes(const pnr_mlp_desc &, int64_t);
-size_t wgrad_workspace_bytes(int, int64_t);
-int launch_wgrad(const float *const *, const float *const *, float *const *, int, int64_t, void *, size_t,
-                 hipStream_t, int arith);
-int launch_fold_bn(const pnr_bn_fold *, int, int64_t, hipStream_t);
-int launch_latent_cl_bwd(const float *, float *const *, const int32_t *, const int32_t *, const int32_t *, int, int, int,
-                         int, hipStream_t);
-int launch_latent_cl(const float *const *, const int32_t *, const int32_t *, const int32_t *, int, int, float *,
-                     int, int, bool, hipStream_t);
-int launch_composite_bwd(const float *, const float *, const float *, int64_t, int, int, const float *,
-                         const float *, const float *, float *, float *, hipStream_t);
-int launch_points_in_bwd(const float *, const float *, int, int64_t, int64_t, int, const float *, const float *,
-                         int, int, float, float, const float *, int, const float *, const float *, float *,
-                         float *, const uint8_t *, hipStream_t);
-int launch_point_mlp(const pnr_scene &, const pnr_mlp_desc &, const void *, const float *,
-                     const float *, int, int64_t, const float *, const float *, int64_t, int64_t,
-                     float *, float *, hipStream_t, float *save = nullptr, const float *proj = nullptr,
-                     const MarchCfg *march = nullptr);
-int sort_width(int n);
-int64_t latent_proj_floats(const pnr_scene &, const pnr_mlp_desc &);
-int launch_latent_proj(const pnr_scene &, const pnr_mlp_weights &, float *, size_t, hipStream_t);
 
 static thread_local char g_err[1024];
 // pnr_render_set_fused: the DEFAULT march mode of calls whose pnr_render_cfg.march_mode is -1:

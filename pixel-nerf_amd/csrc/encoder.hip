@@ -11,6 +11,7 @@
 //   l1 = src - i0, l0 = 1 - l1, i1 = i0 + (i0 < in - 1),
 //   out = l0h (l0w v00 + l1w v01) + l1h (l0w v10 + l1w v11)
 #include "pnr_common.h"
+#include "pnr_launch.h"
 
 namespace pnr {
 

@@ -7,6 +7,7 @@
 // to that wave.  Loads of the (B, K) / (B, K, 4) tensors are coalesced:
 // lane k of chunk c reads sample c*64+k.
 #include "march_dev.h"
+#include "pnr_launch.h"
 
 namespace pnr {
 

@@ -308,11 +308,5 @@ struct MarchCfg {
     // unit i is ray i.  Draws and outputs use the ray's own index, so results do not depend on it.
     const int *order;
 };
-// LDS floats of the fused march region (k_point_mlp): the ray's z (128) | raw (128 x 4), the
-// epilogue scratch w (128) | cdf (128) | sort (128), near / far (4), and with the single-launch
-// march the fine pack's positional-encoding table (32: freqs | phases; the coarse pack's is the
-// kernel's own table)
-constexpr int MARCH_BUF_FLOATS = 640;
-constexpr int MARCH_LDS_FLOATS = MARCH_BUF_FLOATS + 384 + 4 + 32;
 
 }  // namespace pnr

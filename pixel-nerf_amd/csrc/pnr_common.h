@@ -172,7 +172,7 @@ __device__ __forceinline__ float rng_normal(const RngSrc &r, int64_t ray, int wi
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647f * u2);
 }
 
-// ---- exact 3-way bf16 split (split-bf16 products: mlp.hip PREC 6 / 9, wgrad.hip) ------
+// ---- exact 3-way bf16 split (split-bf16 products: mlp_dev.h PREC 6 / 9, wgrad.hip) ------
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -195,6 +195,25 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned &p0, unsig
     p0 = h;
     p1 = m;
     p2 = cvt_pk(t.x, t.y);
+}
+__device__ __forceinline__ f4 mfma_bf(bf8 a, bf8 b, f4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+// ---- two-part fp16 split (f16x3 products: mlp_dev.h PREC 3 / 1, wgrad.hip) ---------------
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ f4 mfma_h(h8 a, h8 b, f4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+// fp16 residuals of a pair: f16(x - f32(h.lo)), f16(y - f32(h.hi)) by v_fma_mix{lo,hi}_f16
+// (the fp16 operand widened in the instruction, one rounding of the exact difference: the
+// same bits as subtracting in fp32 and converting, in 2 instructions instead of 5)
+__device__ __forceinline__ unsigned resid_pk(unsigned h, float x, float y) {
+    unsigned d;
+    asm("v_fma_mixlo_f16 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(x));
+    asm("v_fma_mixhi_f16 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(d) : "v"(h), "v"(y));
+    return d;
 }
 
 }  // namespace pnr

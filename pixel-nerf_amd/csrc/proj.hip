@@ -15,6 +15,7 @@
 // k in chunks of 32 through padded LDS tiles (pitch 33: conflict-free column reads), the
 // next chunk's global loads in flight while the current one is multiplied.
 #include "pnr_common.h"
+#include "pnr_launch.h"
 
 namespace pnr {
 namespace projk {

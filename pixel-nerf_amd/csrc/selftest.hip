@@ -13,8 +13,6 @@
 namespace pnr {
 namespace selftest {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 // lane ^ J by ds_bpermute (__shfl_xor): what march_dev.h's lane_xor uses
 template <int J>
 __device__ __forceinline__ float xor_bperm(float v) { return __shfl_xor(v, J, 64); }
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(64) void k_lane_exchange(const float *__restrict__ 
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc[r][c], 0, 0, 0);
+                for (int c = 0; c < 4; ++c) acc[r][c] = mfma_h(a, b, acc[r][c]);
         }
     }
     auto body = [&]() {

@@ -11,6 +11,7 @@
 // The ResnetFC backward runs as plain per-layer GEMMs on the saved activations
 // (pnr/train.py).
 #include "pnr_common.h"
+#include "pnr_launch.h"
 
 namespace pnr {
 

@@ -49,6 +49,7 @@
 // (dropped terms < 2^-24 |x y|), no scaling (bf16 has fp32's exponent range); one image set,
 // split and MFMAs separated by two barriers per step.
 #include "pnr_common.h"
+#include "pnr_launch.h"
 
 namespace pnr {
 namespace wg {
@@ -75,10 +76,6 @@ typedef __attribute__((address_space(3))) s4 lds_s4;
 
 // image row of point p (0..31) of a step: bits 2 and 3 swapped
 __device__ __forceinline__ int prow(int p) { return (p & ~12) | ((p & 4) << 1) | ((p & 8) >> 1); }
-
-__device__ __forceinline__ f4 mfma_bf(bf8 a, bf8 b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // MFMA operand of 16 columns: lane l receives column c0 + (l & 15), points 8 (l >> 4) ..
 // + 7.  `base` = image + 2 c0 bytes; lo / hi = the lane's byte offsets of its points
@@ -164,10 +161,8 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad(Args a) {
 #pragma unroll 1
     for (int64_t pb = p0; pb < p1; pb += PS) {
         __syncthreads();   // the previous step's fragment reads are done
-#ifndef PNR_WG_NOPUT   // diagnostic ablation (stale images)
         put(imd, sd);
         put(imx, sx);
-#endif
         __syncthreads();
         if (pb + PS < p1) load(pb + PS);   // in flight during this step's MFMAs
         bf8 xb[4][3];
@@ -183,11 +178,9 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad(Args a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 f4 v = acc[i][j];
-#ifndef PNR_WG_MFMA3   // diagnostic ablation: 3 of the 6 products
                 v = mfma_bf(da[2], xb[j][0], v);
                 v = mfma_bf(da[1], xb[j][1], v);
                 v = mfma_bf(da[0], xb[j][2], v);
-#endif
                 v = mfma_bf(da[1], xb[j][0], v);
                 v = mfma_bf(da[0], xb[j][1], v);
                 v = mfma_bf(da[0], xb[j][0], v);
@@ -215,30 +208,12 @@ constexpr int HS_FLAG = HS_MAX + 512 * 4;           // flag[2]: step index of an
 constexpr int LDS_BYTES_H = HS_FLAG + 16;           // 147,472 B
 constexpr int E_UNSET = -100;                       // no nonzero value seen: scale 2^100
 constexpr float OVF = 32768.f;                      // |v 2^-E| >= 2^15: the channel's scale moves
-#ifndef PNR_WGH_HEAD
-#define PNR_WGH_HEAD 5
-#endif
-#ifndef PNR_WGH_INIT
-#define PNR_WGH_INIT 4
-#endif
-constexpr int E_HEAD = PNR_WGH_HEAD;                // a moved channel's maximum lands in [2^H, 2^(H+1))
-constexpr int INIT_STEPS = PNR_WGH_INIT;            // steps whose maxima set the chunk's first scales
+constexpr int E_HEAD = 5;                           // a moved channel's maximum lands in [2^H, 2^(H+1))
+constexpr int INIT_STEPS = 4;                       // steps whose maxima set the chunk's first scales
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ f4 mfma_h(h8 a, h8 b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-// packed fp16 residuals f16(x - f32(h.lo)), f16(y - f32(h.hi)): one rounding of the exact
-// difference (v_fma_mix{lo,hi}_f16, as mlp.hip's split)
-__device__ __forceinline__ unsigned resid_pk(unsigned h, float x, float y) {
-    unsigned d;
-    asm("v_fma_mixlo_f16 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(x));
-    asm("v_fma_mixhi_f16 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(d) : "v"(h), "v"(y));
-    return d;
-}
 __device__ __forceinline__ h8 tr_frag_h(const char *base, int lo, int hi) {
     const s4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(base + lo));
     const s4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(base + hi));
@@ -281,11 +256,7 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
     // (slow path) one step's row of this thread: 4 f4 of dY, 4 of X (columns 8 jc + 0..7,
     // 128 + 8 jc + 0..7); ok = the row is a point of the chunk
     auto load = [&](int step, f4 (&d)[4], f4 (&x)[4], bool &ok) {
-#ifdef PNR_WG_L2ROWS   // diagnostic ablation: every step re-reads the chunk's first rows (L2 hits)
-        const int64_t p = p0 + r + 0 * step;
-#else
         const int64_t p = p0 + (int64_t)step * PS + r;
-#endif
         ok = p < p1;
         const int64_t pc = ok ? p : 0;
 #pragma unroll
@@ -469,9 +440,7 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
                 v = mfma_h(dh, xb[j][0], v);
                 acc[i][j] = v;
             }
-#ifndef PNR_WG_NOPUT   // diagnostic ablation (stale images)
             if (i & 1) put_piece(i >> 1);
-#endif
             dh = nh;
             dl = nl;
         }

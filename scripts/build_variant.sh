@@ -1,19 +1,33 @@
 #!/bin/bash
 # Build an A/B variant of libpnr.so into pixel-nerf_amd/build/<tag>/libpnr.so.
 #   [PATCH=tools/patches/<variant>.diff] scripts/build_variant.sh <tag> <git-rev|WORKTREE> [extra hipcc flags...]
-# The csrc/ sources come from <rev> (or the working tree), with PATCH (a rejected schedule variant,
-# tools/patches/) applied to the copy; the flags select diagnostics (csrc/pnr_diag.h) or the
-# patch's knob.  Select the variant at run time with PNR_LIB_PATH=pixel-nerf_amd/build/<tag>/libpnr.so
-# (diagnostic only).
+# The csrc/ sources come from <rev> (or the working tree), with PATCH (a rejected schedule variant or
+# the ablation knobs, tools/patches/) applied to the copy; the flags select timing diagnostics
+# (csrc/pnr_diag.h) or the patch's knob.  Select the variant at run time with
+# PNR_LIB_PATH=pixel-nerf_amd/build/<tag>/libpnr.so (diagnostic only).
+# The file list is whatever csrc/ holds at <rev>: every *.h, and as translation units every *.hip
+# except selftest.hip (its own library) plus abi.cpp.
 set -euo pipefail
 tag=$1; rev=$2; shift 2
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/pixel-nerf_amd/build/$tag
 src=$out/src
 rm -rf "$out"; mkdir -p "$src/csrc" "$src/include"
-for f in march.hip mlp.hip train.hip encoder.hip bn.hip wgrad.hip proj.hip abi.cpp pnr_common.h march_dev.h pnr_diag.h; do
-  if [ "$rev" = WORKTREE ]; then if [ -f "$root/pixel-nerf_amd/csrc/$f" ]; then cp "$root/pixel-nerf_amd/csrc/$f" "$src/csrc/$f"; fi
-  else git -C "$root" show "$rev:pixel-nerf_amd/csrc/$f" > "$src/csrc/$f" 2>/dev/null || rm -f "$src/csrc/$f"; fi
+if [ "$rev" = WORKTREE ]; then
+  names=$(cd "$root/pixel-nerf_amd/csrc" && ls)
+else
+  names=$(git -C "$root" ls-tree --name-only "$rev:pixel-nerf_amd/csrc")
+fi
+units=()
+for f in $names; do
+  case $f in
+    selftest.hip) continue ;;
+    *.hip|abi.cpp) units+=("$f") ;;
+    *.h) ;;
+    *) continue ;;
+  esac
+  if [ "$rev" = WORKTREE ]; then cp "$root/pixel-nerf_amd/csrc/$f" "$src/csrc/$f"
+  else git -C "$root" show "$rev:pixel-nerf_amd/csrc/$f" > "$src/csrc/$f"; fi
 done
 if [ "$rev" = WORKTREE ]; then cp "$root/include/pnr_abi.h" "$src/include/"
 else git -C "$root" show "$rev:include/pnr_abi.h" > "$src/include/pnr_abi.h"; fi
@@ -24,17 +38,17 @@ fi
 # sources include "../../include/pnr_abi.h" relative to csrc/
 mkdir -p "$out/include"; cp "$src/include/pnr_abi.h" "$out/include/"
 objs=()
-for f in march.hip mlp.hip train.hip encoder.hip bn.hip wgrad.hip proj.hip abi.cpp; do
-  [ -f "$src/csrc/$f" ] || continue   # older revisions lack later files
+pids=()
+for f in "${units[@]}"; do
   mkdir -p "$out/tmp_$f"
   # -save-temps=obj: the device assembly for isa_lint.py (the Makefile's check)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w "$@" -I"$src/csrc" -save-temps=obj \
     -x hip -c "$src/csrc/$f" -o "$out/tmp_$f/$f.o" &
+  pids+=($!)
   objs+=("$out/$f.o")
 done
-wait
-for f in march.hip mlp.hip train.hip encoder.hip bn.hip wgrad.hip proj.hip abi.cpp; do
-  [ -f "$src/csrc/$f" ] || continue
+for p in "${pids[@]}"; do wait "$p"; done   # a failed compile ends the build (set -e)
+for f in "${units[@]}"; do
   mv "$out/tmp_$f/$f.o" "$out/$f.o"
   mv "$out/tmp_$f/"*-hip-amdgcn-amd-amdhsa-gfx950.s "$out/$f.gfx950.s"
   rm -rf "$out/tmp_$f"

@@ -420,12 +420,62 @@ def test_built_device_code_passes_isa_lint():
     if not files:
         pytest.skip("no in-tree build (make -C pixel-nerf_amd)")
     names = {os.path.basename(f) for f in files}
-    assert {"mlp.hip.gfx950.s", "march.hip.gfx950.s", "train.hip.gfx950.s", "wgrad.hip.gfx950.s"} <= names
+    assert {"mlp.hip.gfx950.s", "mlp_pack.hip.gfx950.s", "mlp_bwd.hip.gfx950.s", "march.hip.gfx950.s",
+            "train.hip.gfx950.s", "wgrad.hip.gfx950.s"} <= names
     spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(REPO, "pixel-nerf_amd", "isa_lint.py"))
     lint = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(lint)
     for f in files:
         assert lint.lint_file(f) == [], f
+
+
+_ASM_KERNEL = """\t.text
+\t.globl\tk_a
+\t.p2align\t8
+\t.type\tk_a,@function
+k_a:                                    ; @k_a
+\t.loc\t1 %(line)d 0
+\ts_load_dword s0, s[4:5], 0x0 ; a comment
+.LBB%(fn)d_1:
+\tv_add_f32_e32 v0, %(src)s, v0
+\ts_cbranch_scc1 .LBB%(fn)d_1
+\ts_endpgm
+.Lfunc_end%(fn)d:
+\t.size\tk_a, .Lfunc_end%(fn)d-k_a
+\t.amdhsa_kernel k_a
+\t\t.amdhsa_next_free_vgpr %(vgpr)d
+\t.end_amdhsa_kernel
+"""
+
+
+def test_asm_equal_matches_kernels_by_name_across_files(tmp_path):
+    """tools/asm_equal.py: a kernel that moved to another file, with other label numbers, line
+    info and comments, is SAME; a changed instruction, a changed descriptor or a kernel on one side
+    only is a difference (exit status 1)."""
+    import subprocess
+    import sys
+
+    tool = os.path.join(REPO, "tools", "asm_equal.py")
+
+    def run(name, **kw):
+        a, b = tmp_path / (name + "_a"), tmp_path / (name + "_b")
+        a.mkdir()
+        b.mkdir()
+        (a / "one.hip.gfx950.s").write_text(_ASM_KERNEL % dict(fn=0, line=10, src="v1", vgpr=8))
+        vals = dict(fn=7, line=99, src="v1", vgpr=8)
+        vals.update(kw)
+        (b / "two.hip.gfx950.s").write_text((_ASM_KERNEL % vals).replace("k_a", vals.pop("sym", "k_a")))
+        r = subprocess.run([sys.executable, tool, str(a), str(b)], capture_output=True, text=True)
+        return r.returncode, r.stdout
+
+    rc, out = run("same")
+    assert rc == 0 and out.startswith("SAME kernel k_a (one.hip.gfx950.s -> two.hip.gfx950.s"), out
+    rc, out = run("code", src="v2")
+    assert rc == 1 and "DIFF kernel k_a" in out and "code line" in out, out
+    rc, out = run("desc", vgpr=9)
+    assert rc == 1 and "DIFF kernel k_a" in out and "descriptor" in out, out
+    rc, out = run("only", sym="k_b")
+    assert rc == 1 and "ONLY-A k_a" in out and "ONLY-B k_b" in out, out
 
 
 def test_ray_block_order_groups_neighbouring_pixels():

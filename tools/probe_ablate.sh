@@ -1,5 +1,9 @@
 #!/bin/bash
-# Ablation variants of the fused MLP (built by scripts/build_variant.sh), projected-latent path.
+# Ablation variants of the fused MLP, projected-latent path.  The knobs are not in the product
+# sources; build each variant first (CPU) from the knob patch, e.g.
+#   PATCH=tools/patches/ablations.diff scripts/build_variant.sh gemmonly WORKTREE -DPNR_GEMM_ONLY
+#   PATCH=tools/patches/ablations.diff scripts/build_variant.sh nowstream WORKTREE -DPNR_ABLATE_WSTREAM
+#   PATCH=tools/patches/ablations.diff scripts/build_variant.sh nogather WORKTREE -DPNR_ABLATE_GATHER
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 for t in ${VARIANTS:-default gemmonly nowstream nogather}; do
   lib=pixel-nerf_amd/build/$t/libpnr.so

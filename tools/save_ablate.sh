@@ -2,7 +2,8 @@
 # What the training forward's activation save costs, by part (diagnostic builds, results invalid):
 # tools/fwd_save_ab.py on the shipped library and on builds without the fp32 save-slot stores
 # (savef: -DPNR_ABLATE_SAVEF), without the relu-mask stores (savem: -DPNR_ABLATE_SAVEM) and without
-# both (savefm); scripts/build_variant.sh <name> WORKTREE <flags>.  csrc/pnr_diag.h.
+# both (savefm); PATCH=tools/patches/ablations.diff scripts/build_variant.sh <name> WORKTREE <flags>
+# (the knobs live in that patch, not in the product sources).
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 for lib in ${VARIANTS:-default savef savem savefm}; do
   echo "== $lib"

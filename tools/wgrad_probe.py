@@ -1,5 +1,7 @@
 """Times pnr_weight_grad (k_wgrad + k_wgrad_reduce) alone: 13 layers of 512 x 512 over P points,
-the coarse training MLP's shape.  Select a libpnr.so variant with PNR_LIB_PATH.
+the coarse training MLP's shape.  Select a libpnr.so variant with PNR_LIB_PATH; the ablation variants
+(-DPNR_WG_NOPUT, -DPNR_WG_MFMA3, -DPNR_WG_L2ROWS, -DPNR_WGH_HEAD=h, -DPNR_WGH_INIT=n; results invalid) are built by
+    PATCH=tools/patches/ablations.diff scripts/build_variant.sh NAME WORKTREE -D<knob>
     python tools/wgrad_probe.py [P] [jobs]"""
 import os
 import sys
