@@ -210,7 +210,10 @@ int pnr_point_query(const pnr_scene *scene, const pnr_mlp_desc *desc, const void
 /* ---- full coarse + fine render ------------------------------------------------ */
 /* Replaces: NeRFRenderer.forward(model, rays, want_weights) (nerf.py:251-303)
  * with model = PixelNeRFNet (mlp_coarse / mlp_fine; pass the coarse pack twice when
- * mlp_fine is None, models.py:242). */
+ * mlp_fine is None, models.py:242).  pnr_render_forward* take ONE `desc`: both packs (and
+ * both projections) must come from the same pnr_mlp_desc, since the fine pack is read under
+ * that descriptor's layout (a smaller fine pack would be read past its end).  A model whose
+ * mlp_fine has another n_blocks or min(combine_layer, n_blocks) cannot use these calls. */
 size_t pnr_render_workspace_bytes(const pnr_scene *scene, const pnr_render_cfg *cfg,
                                   int64_t n_rays);
 int pnr_render_forward(const pnr_scene *scene, const pnr_mlp_desc *desc,

@@ -263,7 +263,11 @@ __global__ __launch_bounds__(NTHR) void k_mlp_bwd(BwdArgs a) {
                     }
                 }
             }
-            if (b_lo == 0) store_rows(x, dy_slot(nb, row0), tile, P, wave, lane, bs_slot(nb), first);
+            // dY(lin_in) belongs to the segment that ends the chain: with NS > 1 a view's, never the
+            // per-point one (combine_layer = 0 gives that one b_lo = 0 too, but its x is the undivided
+            // dL/d(mean): it must reach neither dy[nb] nor lin_in's bias partial)
+            if (b_lo == 0 && (sgi > 0 || a.ns == 1))
+                store_rows(x, dy_slot(nb, row0), tile, P, wave, lane, bs_slot(nb), first);
         }
     }
 }

@@ -207,9 +207,13 @@ class ResnetFC(nn.Module):
             return "combine_type %r not implemented" % self.combine_type
         if self.use_spade:
             return "use_spade not implemented"
-        if self.n_blocks > 8:
-            return "n_blocks > 8"
+        if self.n_blocks < 1 or self.n_blocks > 8:
+            return "n_blocks in [1, 8] required (got %d)" % self.n_blocks
         return None
+
+    def n_linz(self):
+        """min(combine_layer, n_blocks): the blocks with a lin_z layer, run per view."""
+        return min(self.combine_layer, self.n_blocks)
 
     def desc(self, pe_n, precision="fp32"):
         return _lib.MlpDesc(self.d_in, self.d_latent, self.d_hidden, self.d_out, self.n_blocks,
@@ -500,6 +504,9 @@ class PixelNeRFNet(nn.Module):
             return "use_global_encoder"
         if self.code is None or not self.code.include_input:
             return "positional encoding must include the input"
+        if 2 * self.code.num_freqs > 16:
+            # pnr_mlp_pack: pe_n (sin / cos columns per coordinate) in [0, 16], d_in <= 64
+            return "positional encoding with num_freqs > 8 (got %d) not implemented" % self.code.num_freqs
         if self.encoder.index_interp != "bilinear" or self.encoder.index_padding != "border":
             return "the fused gather implements bilinear / border indexing"
         for mlp in (self.mlp_coarse, self.mlp_fine):
@@ -507,6 +514,14 @@ class PixelNeRFNet(nn.Module):
                 r = mlp.hip_unsupported_reason()
                 if r:
                     return r
+        c, f = self.mlp_coarse, self.mlp_fine
+        if f is not None and (f.n_blocks, f.n_linz()) != (c.n_blocks, c.n_linz()):
+            # pnr_render_forward* lays out both packs by ONE pnr_mlp_desc (include/pnr_abi.h): a
+            # fine pack of another shape would be read under the coarse layout, past its end if
+            # it is the smaller one
+            return ("mlp_coarse and mlp_fine of different shape (n_blocks %d / %d, lin_z layers %d / %d): "
+                    "the fused render takes one MLP descriptor for both" % (
+                        c.n_blocks, f.n_blocks, c.n_linz(), f.n_linz()))
         return None
 
     def hip_unsupported_reason(self):

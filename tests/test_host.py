@@ -294,6 +294,47 @@ def test_callback_confs_and_state_dict_layout():
     assert PixelNeRFNet(cases["viewdirs"]).d_in == 78
 
 
+def _shape_conf(coarse=(5, 3), fine=(5, 3), num_freqs=6):
+    base = _conf_dict()
+    mlp = lambda nb, cl: dict(base["mlp_coarse"], n_blocks=nb, combine_layer=cl)   # noqa: E731
+    return dict(base, code=dict(base["code"], num_freqs=num_freqs), mlp_coarse=mlp(*coarse), mlp_fine=mlp(*fine))
+
+
+def test_fused_conf_reason_follows_the_library_descriptor_range():
+    """fused_conf_reason mirrors mlp_check_desc (csrc/mlp_pack.hip): pe_n = 2 num_freqs in [0, 16]
+    and n_blocks in [1, 8]; a model outside takes the callback path instead of raising from
+    pnr_mlp_pack."""
+    for nf in (0, 8):
+        net = PixelNeRFNet(_shape_conf(num_freqs=nf))
+        assert net.fused_conf_reason() is None, nf
+        assert net.d_in == 6 + 6 * nf
+    for nf in (9, 10):
+        r = PixelNeRFNet(_shape_conf(num_freqs=nf)).fused_conf_reason()
+        assert r is not None and "positional encoding" in r and str(nf) in r, (nf, r)
+    for nb in (0, 9):
+        r = PixelNeRFNet(_shape_conf((nb, 3), (nb, 3))).fused_conf_reason()
+        assert r is not None and "n_blocks" in r, (nb, r)
+    for nb, cl in ((1, 0), (1, 1), (3, 1000), (8, 8), (8, 0)):
+        assert PixelNeRFNet(_shape_conf((nb, cl), (nb, cl))).fused_conf_reason() is None, (nb, cl)
+
+
+def test_fused_conf_reason_refuses_coarse_and_fine_of_different_shape():
+    """pnr_render_forward* take one pnr_mlp_desc for both packs: a model whose mlp_fine differs
+    from mlp_coarse in n_blocks or min(combine_layer, n_blocks) takes the callback path (its
+    fine pack would be read under the coarse layout).  mlp_fine = None, and combine_layer
+    values that differ only above n_blocks, stay fused."""
+    for coarse, fine in (((5, 3), (3, 1000)), ((3, 1000), (5, 3)), ((5, 3), (5, 2)), ((5, 3), (4, 3))):
+        net = PixelNeRFNet(_shape_conf(coarse, fine))
+        r = net.fused_conf_reason()
+        assert r is not None and "mlp_fine" in r and "different shape" in r, (coarse, fine, r)
+        assert net.hip_unsupported_reason() == r
+        with pytest.raises(NotImplementedError, match="different shape"):
+            net._require_hip()
+        net.mlp_fine = None      # as eval_approx.py:62-63 does
+        assert net.fused_conf_reason() is None, (coarse, fine)
+    assert PixelNeRFNet(_shape_conf((3, 1000), (3, 5))).fused_conf_reason() is None
+
+
 def test_inference_trunk_fold_table_follows_the_module():
     """pnr.encoder.InferenceTrunk (the eval-mode encode) builds its pnr_fold_batchnorm records from
     the LIVE module on every encode: one record per (conv, bn) pair with the tensors' current
