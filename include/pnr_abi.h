@@ -1,12 +1,15 @@
 /*
  * pnr_abi.h — C ABI of the MI355X (gfx950) pixelNeRF ray-march library (libpnr.so).
  *
- * The library replaces the per-ray hot path of the reference (etiiiR/pixel-nerf):
+ * The library replaces the per-ray hot path of the reference (etiiiR/pixel-nerf) and the mesh
+ * step of its evaluation script:
  *   src/render/nerf.py      NeRFRenderer.forward / sample_* / composite  (nerf.py:98-303)
  *   src/model/models.py     PixelNeRFNet.forward                         (models.py:146-266)
  *   src/model/resnetfc.py   ResnetFC / ResnetBlockFC                     (resnetfc.py:10-184)
  *   src/model/code.py       PositionalEncoding                           (code.py:30-42)
  *   src/model/encoder.py    SpatialEncoder.index (grid_sample)           (encoder.py:80-109)
+ *   eval/eval.py            skimage.measure.marching_cubes               (eval.py:105)
+ *   src/util/recon.py       mcubes.marching_cubes                        (recon.py:71)
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer owned by the caller, except the struct
@@ -15,6 +18,8 @@
  *   - Calls are asynchronous and stream-ordered on `stream` (a hipStream_t; NULL
  *     = the default stream).  The library never allocates device memory: scratch
  *     comes from a caller-provided workspace sized by the *_workspace_bytes query.
+ *     One call waits for its stream before it returns: pnr_mc_emit, which reads the two
+ *     counted totals back to check the caller's capacities.  pnr_mc_case_table is host-only.
  *   - Functions return PNR_OK (0) or a negative pnr_status; pnr_last_error()
  *     returns a thread-local message for the last failing call on that thread.
  *     No C++ exception crosses this boundary.
@@ -512,6 +517,63 @@ int pnr_weight_grad(const float *const *dy, const float *const *x, float *const 
 int pnr_weight_grad_arith(const float *const *dy, const float *const *x, float *const *d_weight,
                           int32_t n_layers, int64_t n_points, int32_t arith, void *workspace,
                           size_t workspace_bytes, pnr_stream_t stream);
+
+/* ---- Isosurface extraction (marching cubes; additive in ABI 8) ------------------------------
+ * Replaces: skimage.measure.marching_cubes in eval/eval.py:105 and mcubes.marching_cubes in
+ * src/util/recon.py:71, on a grid that is already on the device.  The output is an INDEXED
+ * mesh, verts (V, 3) float32 and faces (T, 3) int32, every shared vertex once.
+ *
+ *   Grid      (nx, ny, nz) fp32, contiguous, [x][y][z] with z fastest; 1 .. 1024 per axis (larger:
+ *             PNR_ERR_UNSUPPORTED).  Grid point p = (x * ny + y) * nz + z.  A grid with a
+ *             dimension of 1 has no cells: V = T = 0.
+ *   Inside    a corner is inside iff value > level.  NaN compares false: outside, never a fault.
+ *   Vertices  one per grid edge whose two ends differ in that predicate, in index units (as skimage
+ *             returns them).  With a the value at the lower-index end and b at the higher,
+ *             t = (level - a) / (b - a); t = t > 0 ? t : 0 (NaN -> 0); t = t < 1 ? t : 1; the
+ *             coordinate along the edge's axis is index + t, the two others are the indices.  Each
+ *             operation is rounded once to nearest (no contraction), so every cell sharing the
+ *             edge sees the same bits.
+ *   Ownership a grid point owns the three edges leaving it towards +x (axis 0), +y (1), +z (2).
+ *   Order     vertices by (owner grid point, axis); faces by (cell = its minimum corner's grid
+ *             point, position in the case table).  Count pass, exclusive scan, emit pass, no
+ *             atomics: the outputs are bit-identical from run to run.
+ *   Cases     corner k of a cell is (dx, dy, dz) = (k & 1, (k >> 1) & 1, (k >> 2) & 1) and sets bit
+ *             k of the case when inside; edge e = 4 * axis + j runs along `axis` from the corner
+ *             whose two other coordinates (in increasing axis order) are (j & 1, j >> 1).  The
+ *             256-case table is generated (tools/gen_mc_table.py) from the marching-squares
+ *             segments of the six faces; an ambiguous face (two diagonal inside corners) always
+ *             separates its inside corners, a rule of that face's four signs alone, so adjacent
+ *             cells agree and a surface that does not leave the grid is closed.
+ *   Winding   by the right-hand rule a face's normal points towards lower values (skimage's
+ *             gradient_direction = "descent"): a blob of high values has positive signed volume.
+ *   Empty     a surface that leaves the grid is left open at the boundary; a level above the
+ *             maximum or below the minimum gives V = T = 0 and PNR_OK.
+ *
+ * Call order: pnr_mc_count, read the two counts, size verts / faces, pnr_mc_emit with the SAME
+ * grid, dimensions, level and workspace. */
+
+/* Workspace bytes for an (nx, ny, nz) grid: the per-workgroup counts, their scan, the totals and
+ * the edge map (one int32 per (grid point, axis): 12 nx ny nz bytes, 201 MB at 256^3).  0 if a
+ * dimension is outside 1 .. 1024. */
+size_t pnr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+
+/* Count pass and scan.  counts_dev: 2 x int64 on the device, {V, T}, valid once the stream
+ * reaches this point.  Stream-ordered, no host sync. */
+int pnr_mc_count(const float *grid, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
+                 size_t workspace_bytes, int64_t *counts_dev, pnr_stream_t stream);
+
+/* Emit pass after pnr_mc_count on the same arguments: verts (verts_cap, 3) float32, faces
+ * (faces_cap, 3) int32 (NULL allowed with a capacity of 0).  Nothing is stored at or past a
+ * capacity.  After its launches the call waits for the stream and compares the counted totals
+ * with the capacities: smaller ones return PNR_ERR_INVALID (the outputs are then truncated; a
+ * face may hold -1 for a vertex that did not fit). */
+int pnr_mc_emit(const float *grid, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
+                size_t workspace_bytes, float *verts, int64_t verts_cap, int32_t *faces, int64_t faces_cap,
+                pnr_stream_t stream);
+
+/* The case table the kernels use (HOST memory, no device needed): out[case] = up to 5 triangles
+ * as edge triples, -1 padded. */
+int pnr_mc_case_table(int8_t out[256][16]);
 
 #ifdef __cplusplus
 }

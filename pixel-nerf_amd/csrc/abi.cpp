@@ -1,6 +1,7 @@
 // extern "C" entry points of libpnr.so (declared in include/pnr_abi.h):
 // argument validation, workspace carving and the stream-ordered launch
-// sequence of the coarse + fine ray march.  No allocation, no host sync.
+// sequence of the coarse + fine ray march.  No allocation, no host sync (pnr_mc_emit alone
+// waits for its stream: mcubes.hip reads the counted totals back to check the capacities).
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -599,6 +600,42 @@ int pnr_gen_rays(const float *poses, int64_t n_images, int32_t pose_rows, int32_
     if ((reinterpret_cast<uintptr_t>(rays) & 15) != 0) return fail(PNR_ERR_INVALID, "rays must be 16-byte aligned");
     return launch_gen_rays(poses, n_images, pose_rows, width, height, fx, fy, cx, cy, z_near, z_far, rays,
                            (hipStream_t)stream);
+}
+
+size_t pnr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) { return mc_workspace_bytes(nx, ny, nz); }
+
+int pnr_mc_count(const float *grid, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
+                 size_t workspace_bytes, int64_t *counts_dev, pnr_stream_t stream) {
+    if (!grid || !workspace || !counts_dev) return fail(PNR_ERR_INVALID, "pnr_mc_count: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(grid) & 3) != 0) return fail(PNR_ERR_INVALID, "pnr_mc_count: grid must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mc_count: workspace must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(counts_dev) & 7) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mc_count: counts_dev must be 8-byte aligned");
+    return launch_mc_count(grid, nx, ny, nz, level, workspace, workspace_bytes, counts_dev, (hipStream_t)stream);
+}
+
+int pnr_mc_emit(const float *grid, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
+                size_t workspace_bytes, float *verts, int64_t verts_cap, int32_t *faces, int64_t faces_cap,
+                pnr_stream_t stream) {
+    if (!grid || !workspace) return fail(PNR_ERR_INVALID, "pnr_mc_emit: NULL argument");
+    if (verts_cap < 0 || faces_cap < 0 || verts_cap > INT32_MAX || faces_cap > INT32_MAX)
+        return fail(PNR_ERR_INVALID, "pnr_mc_emit: capacities must be in 0 .. 2^31 - 1 (int32 vertex indices)");
+    if ((verts_cap > 0 && !verts) || (faces_cap > 0 && !faces))
+        return fail(PNR_ERR_INVALID, "pnr_mc_emit: NULL output with a non-zero capacity");
+    if ((reinterpret_cast<uintptr_t>(grid) & 3) != 0 || (reinterpret_cast<uintptr_t>(verts) & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(faces) & 3) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mc_emit: grid, verts and faces must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mc_emit: workspace must be 16-byte aligned");
+    return launch_mc_emit(grid, nx, ny, nz, level, workspace, workspace_bytes, verts, verts_cap, faces, faces_cap,
+                          (hipStream_t)stream);
+}
+
+int pnr_mc_case_table(int8_t out[256][16]) {
+    if (!out) return fail(PNR_ERR_INVALID, "pnr_mc_case_table: NULL");
+    mc_case_table(out);
+    return PNR_OK;
 }
 
 }  // extern "C"

@@ -56,5 +56,11 @@ int launch_points_in_bwd(const float *, const float *, int, int64_t, int64_t, in
 // proj.hip
 int64_t latent_proj_floats(const pnr_scene &, const pnr_mlp_desc &);
 int launch_latent_proj(const pnr_scene &, const pnr_mlp_weights &, float *, size_t, hipStream_t);
+// mcubes.hip
+size_t mc_workspace_bytes(int, int, int);
+void mc_case_table(int8_t out[256][16]);
+int launch_mc_count(const float *, int, int, int, float, void *, size_t, int64_t *, hipStream_t);
+int launch_mc_emit(const float *, int, int, int, float, void *, size_t, float *, int64_t, int32_t *, int64_t,
+                   hipStream_t);
 
 }  // namespace pnr

@@ -134,6 +134,11 @@ SIGNATURES = {
                                 c_vp, c_size, c_vp]),
     "pnr_weight_grad_arith": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32,
                                       c_i64, c_i32, c_vp, c_size, c_vp]),
+    # isosurface extraction (csrc/mcubes.hip); pnr_mc_case_table is host-only
+    "pnr_mc_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "pnr_mc_count": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f, c_vp, c_size, c_vp, c_vp]),
+    "pnr_mc_emit": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f, c_vp, c_size, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "pnr_mc_case_table": (c_i32, [c_vp]),
 }
 
 # pnr_weight_grad_arith arithmetics (PNR_WGRAD_*, ABI 4)

@@ -85,3 +85,41 @@ def rng_render_streams(seed, offset, n_rays, n_coarse, n_fine, n_fine_depth, dev
             rng_fill(seed, offset, _lib.RNG_U_FINE, n_rays, nf, device),
             rng_fill(seed, offset, _lib.RNG_U_FINE_JIT, n_rays, nf, device),
             rng_fill(seed, offset, _lib.RNG_N_DEPTH, n_rays, n_fine_depth, device))
+
+
+def marching_cubes(grid, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Isosurface of a device grid (nx, ny, nz) at ``level`` (include/pnr_abi.h, "Isosurface
+    extraction"; csrc/mcubes.hip): ``(verts (V, 3) float32, faces (T, 3) int32)`` on the grid's
+    device, an indexed mesh as skimage.measure.marching_cubes / mcubes.marching_cubes return it
+    (index units, normals towards lower values).  ``verts * spacing + origin`` is applied when either
+    is given.  A level outside the grid's range returns two empty tensors.  One host sync here (the
+    two counts size the outputs); pnr_mc_emit then waits for its own kernels."""
+    grid = _dev(grid, "grid")
+    if grid.dim() != 3:
+        raise ValueError("pnr: grid must be (nx, ny, nz) (got %s)" % (tuple(grid.shape),))
+    nx, ny, nz = (int(s) for s in grid.shape)
+    if min(nx, ny, nz) < 1:
+        raise ValueError("pnr: grid has an empty dimension %s" % (tuple(grid.shape),))
+    lib = _lib.load()
+    dev = grid.device
+    nbytes = lib.pnr_mc_workspace_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise _lib.PnrError("pnr_mc_workspace_bytes: grid %s not supported (1 .. 1024 per axis)" % (
+            tuple(grid.shape),))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    counts = torch.empty(2, device=dev, dtype=torch.int64)
+    st = _lib.stream_of(dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mc_count(_lib.ptr(grid), nx, ny, nz, float(level), _lib.ptr(ws), nbytes,
+                                    _lib.ptr(counts), st), "pnr_mc_count")
+        n_v, n_t = (int(c) for c in counts.cpu())
+        if n_v >= 2 ** 31 or n_t >= 2 ** 31:
+            raise _lib.PnrError("marching_cubes: %d vertices / %d faces do not fit int32 indices" % (n_v, n_t))
+        verts = torch.empty(n_v, 3, device=dev, dtype=torch.float32)
+        faces = torch.empty(n_t, 3, device=dev, dtype=torch.int32)
+        _lib.check(lib.pnr_mc_emit(_lib.ptr(grid), nx, ny, nz, float(level), _lib.ptr(ws), nbytes,
+                                   _lib.ptr(verts) if n_v else None, n_v, _lib.ptr(faces) if n_t else None, n_t,
+                                   st), "pnr_mc_emit")
+    if tuple(spacing) != (1.0, 1.0, 1.0) or tuple(origin) != (0.0, 0.0, 0.0):
+        verts = verts * verts.new_tensor(spacing) + verts.new_tensor(origin)
+    return verts, faces

@@ -10,10 +10,14 @@ skimage's compare_* defaults as pnr.evaluate restates them) into <output>/finish
       --checkpoints_path checkpoints [--split test] [-P "2"] [--mesh_res 256] [--compare]
 
 The reference turns the grid into a mesh with skimage.measure.marching_cubes and trimesh
-(eval.py:104-108); neither is installed offline, so the grid is written as
+(eval.py:104-108) and writes <output>/<object>/<object>_mesh.stl.  --mesh_backend picks the
+extractor: `hip` runs pnr.ops.marching_cubes (csrc/mcubes.hip) on the grid while it is still on the
+device and writes the binary STL with pnr.mesh; `skimage` is the reference's route; `auto` (the
+default) is skimage where skimage and trimesh import and the device path otherwise.  A threshold
+outside the grid's range gives a valid empty STL on the device path.  The grid is also written as
 <output>/<object>/<object>_sigma.npy (float32, relu(sigma), [x][y][z] with torch.meshgrid's 'ij'
-order) and the mesh is exported only where both libraries import.  In the fork the comparison
-after the mesh is unreachable (a `continue` follows the export); --compare runs it."""
+order).  In the fork the comparison after the mesh is unreachable (a `continue` follows the
+export); --compare runs it."""
 import argparse
 import os
 import sys
@@ -26,7 +30,7 @@ sys.path.insert(0, os.path.join(REPO, "pixel-nerf_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pnr import evaluate, util  # noqa: E402
+from pnr import evaluate, mesh, ops, util  # noqa: E402
 from pnr.conf import parse_file  # noqa: E402
 from pnr.data import get_split_dataset  # noqa: E402
 from pnr.models import PRECISIONS, make_model  # noqa: E402
@@ -48,16 +52,44 @@ def density_grid(net, res, device, chunk=CHUNK):
     return torch.relu(out).view(res, res, res)
 
 
-def export_mesh(sig, thresh, path):
-    """The reference's mesh export (eval.py:104-108), where skimage and trimesh are installed."""
+def _have_skimage():
     try:
-        import skimage.measure
-        import trimesh
+        import skimage.measure  # noqa: F401
+        import trimesh  # noqa: F401
     except ImportError:
         return False
-    verts, faces, _, _ = skimage.measure.marching_cubes(sig, level=thresh)
-    trimesh.Trimesh(vertices=verts, faces=faces).export(path)
     return True
+
+
+def export_mesh(sig, thresh, path, backend="auto"):
+    """The reference's mesh export (eval.py:104-108) of the grid `sig` (a device tensor, or a numpy
+    array) to a binary STL at `path`.  Returns (backend used, triangles written, seconds spent
+    extracting).  `hip`: pnr.ops.marching_cubes on the device grid + pnr.mesh.write_stl (an empty
+    surface writes an empty STL); `skimage`: skimage + trimesh; `auto`: skimage where both import,
+    else hip."""
+    if backend == "auto":
+        backend = "skimage" if _have_skimage() else "hip"
+    if backend == "skimage":
+        import skimage.measure
+        import trimesh
+
+        sig_np = sig.cpu().numpy() if torch.is_tensor(sig) else sig
+        t0 = time.perf_counter()
+        verts, faces, _, _ = skimage.measure.marching_cubes(sig_np, level=thresh)
+        dt = time.perf_counter() - t0
+        trimesh.Trimesh(vertices=verts, faces=faces).export(path)
+        return backend, int(len(faces)), dt
+    if backend != "hip":
+        raise ValueError("mesh backend %r (auto, hip, skimage)" % (backend,))
+    if not torch.is_tensor(sig):
+        sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float32)).cuda()
+    torch.cuda.synchronize(sig.device)
+    t0 = time.perf_counter()
+    verts, faces = ops.marching_cubes(sig, thresh)
+    torch.cuda.synchronize(sig.device)
+    dt = time.perf_counter() - t0
+    mesh.write_stl(path, verts, faces)
+    return backend, int(faces.shape[0]), dt
 
 
 def main(argv=None):
@@ -73,6 +105,9 @@ def main(argv=None):
     ap.add_argument("--output", "-O", default="eval")
     ap.add_argument("--mesh_res", type=int, default=256)
     ap.add_argument("--mesh_thresh", type=float, default=0.1)
+    ap.add_argument("--mesh_backend", choices=("auto", "hip", "skimage"), default="auto",
+                    help="isosurface extractor: hip = the device kernels, skimage = the reference's libraries, "
+                         "auto = skimage where skimage and trimesh import, else hip")
     ap.add_argument("--compare", action="store_true", help="render and score the non-source views")
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
@@ -121,12 +156,14 @@ def main(argv=None):
             sig = density_grid(net, args.mesh_res, device)
             torch.cuda.synchronize(device)
             dt = time.perf_counter() - t0
-            sig_np = sig.cpu().numpy()
-            np.save(os.path.join(out_dir, name + "_sigma.npy"), sig_np)
-            meshed = export_mesh(sig_np, args.mesh_thresh, os.path.join(out_dir, name + "_mesh.stl"))
-            print("%s: density grid %d^3 in %.3f s (%.1f M points/s)%s" % (
-                name, args.mesh_res, dt, args.mesh_res ** 3 / dt / 1e6,
-                "" if meshed else "; mesh export skipped (skimage / trimesh not installed)"), flush=True)
+            # the device extractor reads the grid tensor where it is, before the host copy
+            backend, n_tri, dt_mesh = export_mesh(sig, args.mesh_thresh, os.path.join(out_dir, name + "_mesh.stl"),
+                                                  args.mesh_backend)
+            np.save(os.path.join(out_dir, name + "_sigma.npy"), sig.cpu().numpy())
+            print("%s: density grid %d^3 in %.3f s (%.1f M points/s); mesh (%s) %d triangles in %.4f s%s" % (
+                name, args.mesh_res, dt, args.mesh_res ** 3 / dt / 1e6, backend, n_tri, dt_mesh,
+                "" if n_tri else ": threshold %g is outside the grid's range, empty STL written" % args.mesh_thresh),
+                flush=True)
             if not args.compare:
                 continue
             tgt = ~src
