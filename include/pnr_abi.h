@@ -10,11 +10,14 @@
  *   src/model/encoder.py    SpatialEncoder.index (grid_sample)           (encoder.py:80-109)
  *   eval/eval.py            skimage.measure.marching_cubes               (eval.py:105)
  *   src/util/recon.py       mcubes.marching_cubes                        (recon.py:71)
+ *   eval/calc_metrics.py    skimage compare_ssim / compare_psnr          (calc_metrics.py:188-191)
+ *   eval/eval_approx.py     the same two scores per rendered view
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer owned by the caller, except the struct
  *     arguments themselves (host memory, read during the call only).
- *   - All tensors are fp32, C-contiguous, row-major, in the shapes given below.
+ *   - All tensors are fp32, C-contiguous, row-major, in the shapes given below (one exception:
+ *     the float64 `out` of pnr_image_metrics).
  *   - Calls are asynchronous and stream-ordered on `stream` (a hipStream_t; NULL
  *     = the default stream).  The library never allocates device memory: scratch
  *     comes from a caller-provided workspace sized by the *_workspace_bytes query.
@@ -574,6 +577,40 @@ int pnr_mc_emit(const float *grid, int32_t nx, int32_t ny, int32_t nz, float lev
 /* The case table the kernels use (HOST memory, no device needed): out[case] = up to 5 triangles
  * as edge triples, -1 padded. */
 int pnr_mc_case_table(int8_t out[256][16]);
+
+/* ---- Image metrics (per-image MSE and mean SSIM; additive in ABI 8) --------------------------
+ * Replaces: skimage.measure.compare_ssim(multichannel=True) / compare_psnr in
+ * eval/calc_metrics.py:188-191 and eval/eval_approx.py, on images that are already on the device.
+ *
+ *   Inputs    x, y (n, h, w, c) fp32, contiguous, channels last (what the renderer returns);
+ *             n >= 1, c in 1 .. 4, h and w in 7 .. 8192 (larger: PNR_ERR_UNSUPPORTED, as is a
+ *             batch that needs 2^24 or more workgroups: n * c * ceil((h - 6) / T) *
+ *             ceil((w - 6) / T) with T = PNR_IMAGE_METRICS_TILE).
+ *   SSIM      skimage's defaults: 7 x 7 uniform window, sample covariance (cov_norm = 49 / 48),
+ *             C1 = (k1 R)^2, C2 = (k2 R)^2 with R = data_range; the map is evaluated at the
+ *             (h - 6) x (w - 6) pixels whose window lies inside the image (no boundary mode enters),
+ *             averaged per channel, then over the channels.
+ *   MSE       the mean over all h * w * c elements.  PSNR = 10 log10(R^2 / mse) is left to the
+ *             caller (+inf at mse = 0).
+ *   Numerics  the fp32 inputs are widened exactly; window moments, the SSIM expression and every
+ *             sum are fp64.  data_range, k1 and k2 are each read as the shortest decimal that
+ *             rounds to the float passed (0.03f means 0.03, not 0.0299999993...): C2 enters the
+ *             result at full fp64 precision.
+ *   Order     one partial per (image, channel, tile), summed per channel in ascending tile order,
+ *             then over the channels; no atomics.  A row of `out` is bit-identical from run to run
+ *             and whether its image is scored alone or inside a batch.
+ *   NaN       a NaN anywhere in image i of x or y makes row i of `out` NaN and no other row.
+ *
+ * out: (n, 2) FLOAT64 on the device, {mse, ssim} per image, 8-byte aligned like the workspace.
+ * Two launches, stream-ordered, no host sync. */
+#define PNR_IMAGE_METRICS_TILE 16 /* edge of the SSIM-map tile of one workgroup */
+
+/* Workspace bytes (the per-workgroup partials), 0 for any shape pnr_image_metrics would refuse. */
+size_t pnr_image_metrics_workspace_bytes(int64_t n, int32_t h, int32_t w, int32_t c);
+
+int pnr_image_metrics(const float *x, const float *y, int64_t n, int32_t h, int32_t w, int32_t c,
+                      float data_range, float k1, float k2, void *workspace, size_t workspace_bytes,
+                      double *out, pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

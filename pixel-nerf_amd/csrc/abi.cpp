@@ -638,4 +638,21 @@ int pnr_mc_case_table(int8_t out[256][16]) {
     return PNR_OK;
 }
 
+size_t pnr_image_metrics_workspace_bytes(int64_t n, int32_t h, int32_t w, int32_t c) {
+    return image_metrics_workspace_bytes(n, h, w, c);
+}
+
+int pnr_image_metrics(const float *x, const float *y, int64_t n, int32_t h, int32_t w, int32_t c, float data_range,
+                      float k1, float k2, void *workspace, size_t workspace_bytes, double *out,
+                      pnr_stream_t stream) {
+    if (!x || !y || !out) return fail(PNR_ERR_INVALID, "pnr_image_metrics: NULL argument");
+    if (!(data_range > 0.f)) return fail(PNR_ERR_INVALID, "pnr_image_metrics: data_range must be > 0");
+    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 3) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_image_metrics: x and y must be 4-byte aligned");
+    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_image_metrics: out and workspace must be 8-byte aligned");
+    return launch_image_metrics(x, y, n, h, w, c, data_range, k1, k2, workspace, workspace_bytes, out,
+                                (hipStream_t)stream);
+}
+
 }  // extern "C"

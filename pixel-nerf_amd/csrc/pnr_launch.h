@@ -62,5 +62,9 @@ void mc_case_table(int8_t out[256][16]);
 int launch_mc_count(const float *, int, int, int, float, void *, size_t, int64_t *, hipStream_t);
 int launch_mc_emit(const float *, int, int, int, float, void *, size_t, float *, int64_t, int32_t *, int64_t,
                    hipStream_t);
+// metrics.hip
+size_t image_metrics_workspace_bytes(int64_t, int, int, int);
+int launch_image_metrics(const float *, const float *, int64_t, int, int, int, float, float, float, void *, size_t,
+                         double *, hipStream_t);
 
 }  // namespace pnr

@@ -139,6 +139,9 @@ SIGNATURES = {
     "pnr_mc_count": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f, c_vp, c_size, c_vp, c_vp]),
     "pnr_mc_emit": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f, c_vp, c_size, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pnr_mc_case_table": (c_i32, [c_vp]),
+    # per-image MSE / SSIM (csrc/metrics.hip); out is float64
+    "pnr_image_metrics_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "pnr_image_metrics": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_vp, c_size, c_vp, c_vp]),
 }
 
 # pnr_weight_grad_arith arithmetics (PNR_WGRAD_*, ABI 4)

@@ -17,7 +17,7 @@ import torch
 
 from . import util
 
-__all__ = ["ssim", "psnr_np", "select_views", "eval_approx"]
+__all__ = ["ssim", "psnr_np", "image_metrics", "select_views", "eval_approx"]
 
 
 def psnr_np(pred, target, data_range=1.0):
@@ -54,6 +54,29 @@ def ssim(x, y, data_range=1.0, win_size=7, k1=0.01, k2=0.03):
     return float(np.mean(vals))
 
 
+def image_metrics(x, y, backend="numpy"):
+    """(psnr list, ssim list) of two (N, H, W, C) stacks in [0, 1] at data_range 1.  ``"numpy"``
+    scores image by image on the host with ``psnr_np`` / ``ssim`` (tensors are copied there);
+    ``"hip"`` scores the stack on its device (``ops.image_metrics``, float32 tensors or arrays,
+    moved to the current HIP device if they are on the host) with one readback."""
+    if backend == "numpy":
+        if torch.is_tensor(x):
+            x = x.detach().cpu().numpy()
+        if torch.is_tensor(y):
+            y = y.detach().cpu().numpy()
+        assert len(x) == len(y), (len(x), len(y))
+        return [float(psnr_np(a, b)) for a, b in zip(x, y)], [ssim(a, b) for a, b in zip(x, y)]
+    if backend != "hip":
+        raise ValueError("metrics backend must be 'numpy' or 'hip' (got %r)" % (backend,))
+    from . import ops
+
+    x, y = (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, np.float32)) for t in (x, y))
+    dev = x.device if x.device.type == "cuda" else (y.device if y.device.type == "cuda" else torch.device("cuda"))
+    psnr, ssim_ = ops.image_metrics(x.to(dev), y.to(dev))
+    both = torch.stack([psnr, ssim_]).cpu()
+    return both[0].tolist(), both[1].tolist()
+
+
 def select_views(sb, nv, source):
     """(src_view (SB, NS), dest_view (SB, 1)) as eval_approx.py:111-118 draws them."""
     source = torch.as_tensor(source, dtype=torch.long).reshape(-1)
@@ -69,9 +92,13 @@ def select_views(sb, nv, source):
 
 
 def eval_approx(net, renderer, dset, device, source=(64,), batch_size=4, seed=1234, coarse=False,
-                ray_batch_size=50000, gpu_ids=None, log=None):
+                ray_batch_size=50000, gpu_ids=None, log=None, metrics_backend="numpy"):
     """eval_approx.py:56-153 on an already built net / renderer / dataset.  Returns
-    {"psnr": [...], "ssim": [...], "mean_psnr", "mean_ssim", "objects"}."""
+    {"psnr": [...], "ssim": [...], "mean_psnr", "mean_ssim", "objects"}.  ``metrics_backend``:
+    ``"numpy"`` copies each rendered batch to the host and scores it there, ``"hip"`` scores it on
+    the device (``image_metrics``)."""
+    if metrics_backend not in ("numpy", "hip"):
+        raise ValueError("metrics_backend must be 'numpy' or 'hip' (got %r)" % (metrics_backend,))
     if coarse:
         net.mlp_fine = None
     renderer.eval_batch_size = ray_batch_size
@@ -101,12 +128,18 @@ def eval_approx(net, renderer, dset, device, source=(64,), batch_size=4, seed=12
             pri_poses = util.batched_index_select_nd(poses, src_view)
             net.encode(pri_images.to(device=device), pri_poses.to(device=device), focal.to(device=device))
             rgb_fine, _ = render_par(all_rays.to(device=device))
-            rgb_fine = rgb_fine.reshape(SB, H, W, 3).cpu().numpy()
             gt = util.batched_index_select_nd(images_0to1, dest_view).reshape(SB, 3, H, W)
-            gt = gt.permute(0, 2, 3, 1).contiguous().numpy()
-            for sb in range(SB):
-                ssims.append(ssim(rgb_fine[sb], gt[sb]))
-                psnrs.append(psnr_np(rgb_fine[sb], gt[sb]))
+            if metrics_backend == "numpy":
+                rgb_fine = rgb_fine.reshape(SB, H, W, 3).cpu().numpy()
+                gt = gt.permute(0, 2, 3, 1).contiguous().numpy()
+                for sb in range(SB):
+                    ssims.append(ssim(rgb_fine[sb], gt[sb]))
+                    psnrs.append(psnr_np(rgb_fine[sb], gt[sb]))
+            else:   # the render stays on its device, the ground truth goes to it
+                gt = gt.to(device=rgb_fine.device, dtype=torch.float32).permute(0, 2, 3, 1)
+                p, s = image_metrics(rgb_fine.reshape(SB, H, W, 3).float(), gt, metrics_backend)
+                psnrs.extend(p)
+                ssims.extend(s)
             if log is not None:
                 log("curr psnr %.4f ssim %.4f" % (np.mean(psnrs), np.mean(ssims)))
     assert ns >= 1

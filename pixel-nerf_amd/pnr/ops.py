@@ -123,3 +123,50 @@ def marching_cubes(grid, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0))
     if tuple(spacing) != (1.0, 1.0, 1.0) or tuple(origin) != (0.0, 0.0, 0.0):
         verts = verts * verts.new_tensor(spacing) + verts.new_tensor(origin)
     return verts, faces
+
+
+# edge of the SSIM-map tile one workgroup of pnr_image_metrics scores (PNR_IMAGE_METRICS_TILE,
+# include/pnr_abi.h): a (T + 6) x (T + 6) image is exactly one tile
+IMAGE_METRICS_TILE = 16
+
+
+def image_metrics(x, y, data_range=1.0, k1=0.01, k2=0.03):
+    """PSNR and mean SSIM per image of two device stacks (include/pnr_abi.h, "Image metrics";
+    csrc/metrics.hip): x, y (N, H, W, C) or (H, W, C) float32, channels last -> ``(psnr (N,),
+    ssim (N,))`` float64 on their device.  The scores are those of ``evaluate.psnr_np`` /
+    ``evaluate.ssim`` (skimage compare_psnr / compare_ssim(multichannel=True) defaults); psnr is
+    +inf where the images are equal.  No host sync."""
+    for t, name in ((x, "x"), (y, "y")):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+    if y.device != x.device:
+        raise ValueError("pnr: y is on %s, x on %s" % (y.device, x.device))
+    if tuple(y.shape) != tuple(x.shape):
+        raise ValueError("pnr: y has shape %s, x %s" % (tuple(y.shape), tuple(x.shape)))
+    x = _dev(x, "x")
+    y = _dev(y, "y")
+    if x.dim() == 3:
+        x, y = x[None], y[None]
+    if x.dim() != 4:
+        raise ValueError("pnr: x must be (N, H, W, C) or (H, W, C) (got %s)" % (tuple(x.shape),))
+    n, h, w, c = (int(s) for s in x.shape)
+    if not float(data_range) > 0.0:
+        raise ValueError("pnr: data_range must be > 0 (got %r)" % (data_range,))
+    if min(h, w) < 7:
+        raise ValueError("pnr: x is %d x %d, smaller than the 7 x 7 SSIM window" % (h, w))
+    if n < 1 or not 1 <= c <= 4:
+        raise ValueError("pnr: x must hold at least one image of 1 .. 4 channels (got %s)" % (tuple(x.shape),))
+    lib = _lib.load()
+    dev = x.device
+    nbytes = lib.pnr_image_metrics_workspace_bytes(n, h, w, c)
+    if nbytes == 0:
+        raise _lib.PnrError("pnr_image_metrics_workspace_bytes: shape %s not supported (H, W <= 8192, fewer "
+                            "than 2^24 tiles)" % (tuple(x.shape),))
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    out = torch.empty(n, 2, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_image_metrics(_lib.ptr(x), _lib.ptr(y), n, h, w, c, float(data_range), float(k1),
+                                         float(k2), _lib.ptr(ws), nbytes, _lib.ptr(out), _lib.stream_of(dev)),
+                   "pnr_image_metrics")
+    psnr = 10.0 * torch.log10(float(data_range) ** 2 / out[:, 0])
+    return psnr, out[:, 1]

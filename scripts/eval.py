@@ -17,7 +17,8 @@ default) is skimage where skimage and trimesh import and the device path otherwi
 outside the grid's range gives a valid empty STL on the device path.  The grid is also written as
 <output>/<object>/<object>_sigma.npy (float32, relu(sigma), [x][y][z] with torch.meshgrid's 'ij'
 order).  In the fork the comparison after the mesh is unreachable (a `continue` follows the
-export); --compare runs it."""
+export); --compare runs it, and --metrics_backend hip scores its views on the device
+(pnr.ops.image_metrics, csrc/metrics.hip) instead of copying them to the host for numpy / scipy."""
 import argparse
 import os
 import sys
@@ -109,6 +110,9 @@ def main(argv=None):
                     help="isosurface extractor: hip = the device kernels, skimage = the reference's libraries, "
                          "auto = skimage where skimage and trimesh import, else hip")
     ap.add_argument("--compare", action="store_true", help="render and score the non-source views")
+    ap.add_argument("--metrics_backend", choices=("numpy", "hip"), default="numpy",
+                    help="where --compare scores the views: numpy = on the host, image by image; hip = on the "
+                         "device (pnr.ops.image_metrics)")
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
     ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
@@ -171,10 +175,16 @@ def main(argv=None):
             rays = util.gen_rays(poses[tgt].to(device), W, H, focal, dset.z_near, dset.z_far, c=c).reshape(-1, 8)
             with torch.no_grad():
                 rgb = torch.cat([render_par(r[None])[0][0] for r in torch.split(rays, args.ray_batch_size, dim=0)])
-            rgb = rgb.clamp(0.0, 1.0).reshape(-1, H, W, 3).cpu().numpy()
-            gt = (images[tgt] * 0.5 + 0.5).permute(0, 2, 3, 1).numpy()
-            psnr = float(np.mean([evaluate.psnr_np(rgb[i], gt[i]) for i in range(len(gt))]))
-            ssim = float(np.mean([evaluate.ssim(rgb[i], gt[i]) for i in range(len(gt))]))
+            gt = (images[tgt] * 0.5 + 0.5).permute(0, 2, 3, 1)
+            if args.metrics_backend == "numpy":
+                rgb = rgb.clamp(0.0, 1.0).reshape(-1, H, W, 3).cpu().numpy()
+                gt = gt.numpy()
+                psnr = float(np.mean([evaluate.psnr_np(rgb[i], gt[i]) for i in range(len(gt))]))
+                ssim = float(np.mean([evaluate.ssim(rgb[i], gt[i]) for i in range(len(gt))]))
+            else:   # all views of the object in one call, on the device the render is on
+                psnrs, ssims = evaluate.image_metrics(rgb.clamp(0.0, 1.0).reshape(-1, H, W, 3).float(),
+                                                      gt.to(device=device, dtype=torch.float32), "hip")
+                psnr, ssim = float(np.mean(psnrs)), float(np.mean(ssims))
             print("PSNR: %.2f, SSIM: %.4f" % (psnr, ssim), flush=True)
             finish.write("%s %.2f %.4f 1\n" % (name, psnr, ssim))
         except Exception as e:   # eval.py:146-149: report the object and go on

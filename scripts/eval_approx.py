@@ -3,7 +3,11 @@
 SRN-layout dataset, one random target view per object (pnr.evaluate.eval_approx).
 
   python scripts/eval_approx.py -c conf/exp/srn.conf -D <datadir>/cars -n srn_car \
-      --checkpoints_path checkpoints [--split test] [-P "64"] [--coarse] [--seed 1234]
+      --checkpoints_path checkpoints [--split test] [-P "64"] [--coarse] [--seed 1234] \
+      [--metrics_backend hip]
+
+--metrics_backend hip keeps each rendered batch on the device and scores it there
+(pnr.ops.image_metrics); the default, numpy, copies it to the host and scores it image by image.
 
 The conf is read with pnr.conf.parse_file (HOCON subset; pyhocon is absent offline) and the
 checkpoint with PixelNeRFNet.load_weights (torch.load, weights_only=True).
@@ -38,6 +42,9 @@ def main():
     ap.add_argument("--coarse", action="store_true")
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
+    ap.add_argument("--metrics_backend", choices=("numpy", "hip"), default="numpy",
+                    help="where the views are scored: numpy = on the host, image by image; hip = on the device "
+                         "(pnr.ops.image_metrics)")
     ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
                     help="arithmetic of the fused MLP (pnr.models.PRECISIONS); f16 trades accuracy below an "
                          "8-bit step for time")
@@ -53,7 +60,8 @@ def main():
     renderer = NeRFRenderer.from_conf(conf["renderer"], eval_batch_size=args.ray_batch_size).to(device=dev)
     res = evaluate.eval_approx(net, renderer, dset, dev, source=[int(s) for s in args.source.split()],
                                batch_size=args.batch_size, seed=args.seed, coarse=args.coarse,
-                               ray_batch_size=args.ray_batch_size, log=print)
+                               ray_batch_size=args.ray_batch_size, log=print,
+                               metrics_backend=args.metrics_backend)
     print("final psnr", res["mean_psnr"], "ssim", res["mean_ssim"])
 
 
