@@ -300,6 +300,20 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc,
  * Returns the previous default. */
 int32_t pnr_render_set_fused(int32_t on);
 
+/* The fused point model (k_point_mlp) has a lean instantiation for the launches of a render of ONE
+ * source view on the projected latent by a per-pass fused march (march modes 1 and 2), without an
+ * activation save, in precision f16x3 or f16: the paths such a launch never takes are compiled
+ * out, and the tile index, the ray and the camera row are scalar registers.  Its outputs are
+ * bit-identical to the general kernel's.  pnr_mlp_set_lean(0) makes every launch of the process
+ * take the general kernel (tests, A/B runs); nonzero restores the default (on).  Returns the
+ * previous setting.  pnr_mlp_last_kernel: the kernel the process's last point-model launch took
+ * (any thread), PNR_MLP_KERNEL_NONE before the first.  Additive in ABI 8. */
+#define PNR_MLP_KERNEL_NONE 0
+#define PNR_MLP_KERNEL_GENERAL 1
+#define PNR_MLP_KERNEL_LEAN 2
+int32_t pnr_mlp_set_lean(int32_t on);
+int32_t pnr_mlp_last_kernel(void);
+
 /* ---- building blocks (also the generic model-callback path) ------------------ */
 /* Replaces: NeRFRenderer.sample_coarse (nerf.py:98-118).  z (n_rays, n_coarse). */
 int pnr_sample_coarse(const float *rays, int64_t n_rays, int32_t n_coarse,

@@ -509,6 +509,8 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
 }
 
 int32_t pnr_render_set_fused(int32_t on) { return g_fused_default.exchange(on < 0 || on > 3 ? 2 : on); }
+int32_t pnr_mlp_set_lean(int32_t on) { return pnr::mlp_set_lean(on); }
+int32_t pnr_mlp_last_kernel(void) { return pnr::mlp_last_kernel(); }
 
 int pnr_sample_coarse(const float *rays, int64_t n_rays, int32_t n_coarse, const float *u_coarse,
                       int32_t lindisp, float *z, pnr_stream_t stream) {

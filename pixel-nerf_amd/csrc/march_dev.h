@@ -26,13 +26,26 @@ __device__ __forceinline__ float linspace_at(int i, int n, float end, float step
     return (i < n / 2) ? mul_rn(step, (float)i) : sub_rn(end, mul_rn(step, (float)(n - 1 - i)));
 }
 
+// the constants of a pass's coarse draw: they depend on kc alone (k_point_mlp's lean instantiation
+// computes them once per workgroup, coarse_z per call)
+struct CoarseSteps {
+    float end, lstep, step;
+};
+__device__ __forceinline__ CoarseSteps coarse_steps(int kc) {
+    CoarseSteps s;
+    s.end = (float)(1.0 - 1.0 / (double)kc);
+    s.lstep = (kc > 1) ? __fdiv_rn(s.end, (float)(kc - 1)) : 0.0f;
+    s.step = (float)(1.0 / (double)kc);
+    return s;
+}
+__device__ __forceinline__ float coarse_z_at(const RngSrc &u, int64_t b, int kc, int k, float near, float far,
+                                             bool lindisp, const CoarseSteps &s) {
+    const float t = add_rn(linspace_at(k, kc, s.end, s.lstep), mul_rn(rng_uniform(u, b, kc, k), s.step));
+    return t_to_z(t, near, far, lindisp);
+}
 __device__ __forceinline__ float coarse_z(const RngSrc &u, int64_t b, int kc, int k, float near, float far,
                                           bool lindisp) {
-    const float end = (float)(1.0 - 1.0 / (double)kc);
-    const float lstep = (kc > 1) ? __fdiv_rn(end, (float)(kc - 1)) : 0.0f;
-    const float step = (float)(1.0 / (double)kc);
-    const float t = add_rn(linspace_at(k, kc, end, lstep), mul_rn(rng_uniform(u, b, kc, k), step));
-    return t_to_z(t, near, far, lindisp);
+    return coarse_z_at(u, b, kc, k, near, far, lindisp, coarse_steps(kc));
 }
 
 // ---- composite — nerf.py:176-249 ------------------------------------------------------------

@@ -28,6 +28,7 @@
 //     multi-view mean and the head (fp32 from the accumulators).
 // Diagnostic build knobs: pnr_diag.h.
 #include "pnr_diag.h"
+#include <atomic>
 #include <cstddef>
 
 // the timing builds' counters live in this translation unit alone (pnr_diag.h's stamps add to them)
@@ -149,11 +150,27 @@ __device__ __forceinline__ void march_epilogue(const Args &a, int64_t b, const f
     else march_ray<2>(a, b, buf, nf, scr, lane, fine_pass);
 }
 
+// Loads of launch inputs that no kernel of the launch writes (rays, cameras, ray order), through the
+// constant address space: with a wave-uniform address they are scalar loads into SGPRs.
+typedef const __attribute__((address_space(4))) float *CFloatPtr;
+typedef const __attribute__((address_space(4))) int *CIntPtr;
+__device__ __forceinline__ CFloatPtr as_const(const float *p) { return (CFloatPtr)(uint64_t)p; }
+__device__ __forceinline__ CIntPtr as_const(const int *p) { return (CIntPtr)(uint64_t)p; }
+
 // PZ: lin_z from the projected latent (gather_proj) instead of the latent gather + GEMM;
 // MARCH: the fused ray march (a.m), a separate instantiation so that the plain point model
-// keeps its own register allocation
-template <int PREC, bool PZ, bool MARCH>
+// keeps its own register allocation;
+// LEAN: the render of one source view by a per-pass fused march (modes 1 and 2) without an
+// activation save, which is every launch of the headline (launch_point_mlp selects it).  What such
+// a launch never takes is compiled out -- the view loop and the multi-view sum, the activation
+// save, the single-launch march's fine tiles, the point-query loads -- and what is the same for
+// all 512 threads of a tile is scalar: the tile index, the unit's ray (origin, direction, near /
+// far) and the object's camera row are SGPRs loaded by scalar loads, not per-lane copies.  The
+// per-lane arithmetic is the general kernel's, op for op, so the outputs are bit-identical
+// (tests/test_gpu_mlp_lean.py).
+template <int PREC, bool PZ, bool MARCH, bool LEAN = false>
 __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
+    static_assert(!LEAN || (PZ && MARCH && is_h(PREC)), "LEAN is the fused-march render on the projected latent");
     constexpr int KD = H_DIST;   // weight ring distance
     constexpr bool HP = is_h(PREC);      // a scaled-fp16 mode: f16x3 (3) or f16 (1)
     constexpr int NP = nparts(PREC);     // parts of the 512-wide layers' weights and of the publish
@@ -232,9 +249,11 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             lds_barrier();
     };
     auto publish_relu = [&](const Acc &acc, int64_t tile, int save_idx, int64_t row0) {
-        if (a.save) {
-            save_relu(acc, sv_slot(save_idx) + row0 * H, tile, P, wave, lane);
-            save_mask(acc, sv_mask + PS * 16 * save_idx + row0 * 16, tile, P, wave, lane);
+        if constexpr (!LEAN) {
+            if (a.save) {
+                save_relu(acc, sv_slot(save_idx) + row0 * H, tile, P, wave, lane);
+                save_mask(acc, sv_mask + PS * 16 * save_idx + row0 * 16, tile, P, wave, lane);
+            }
         }
         if constexpr (HP) {
             // (phase-timing slots 17, 13-15, 16: glue split into the ring prime / bias loads
@@ -271,12 +290,44 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     const int kpt = MARCH ? march_cfg(a)->kpt : 1;   // tiles per ray and pass when marching
     // tiles per scheduling unit (a ray when marching): its kpt tiles, and with the single-launch
     // march (m.single) its kpt_f fine tiles after them
-    const bool single = MARCH && march_cfg(a)->single;
+    const bool single = !LEAN && MARCH && march_cfg(a)->single;   // (LEAN: false at compile time)
     const int upt = single ? kpt + march_cfg(a)->kpt_f : kpt;
     // single launch: the fine tiles' PE table from the fine pack's header (the packs
     // of two MLPs may carry different tables); visible after the first barrier
     float *petab_f = inbuf + M.petab_f;
     if (single && wave == 1) petab_f[lane & 31] = march_cfg(a)->packed_f[lane & 31];
+    // the projection's launch constants (models.py:206-212 -> encoder.py:95-108): the latent size as
+    // floats, the pixel -> grid scales and the half extents
+    struct ProjK {
+        float wlf, hlf, kx, ky, hx, hy;
+    };
+    auto proj_consts = [&]() -> ProjK {
+        const float wlf = (float)a.wl, hlf = (float)a.hl;
+        const float lsx = mul_rn(__fdiv_rn(wlf, sub_rn(wlf, 1.f)), 2.f);
+        const float lsy = mul_rn(__fdiv_rn(hlf, sub_rn(hlf, 1.f)), 2.f);
+        return ProjK{wlf, hlf, __fdiv_rn(lsx, a.img_w), __fdiv_rn(lsy, a.img_h), mul_rn(sub_rn(wlf, 1.f), 0.5f),
+                     mul_rn(sub_rn(hlf, 1.f), 0.5f)};
+    };
+    // LEAN: ltab, the launch constants that a tile's features need, computed once (every lane
+    // computes the same values; wave 0 stores them, visible after the first barrier).  Computed in
+    // the loop they are hoisted out of it as uniform floats in VGPRs that live across every tile,
+    // which the allocator spills to scratch and reloads in each tile's feature phase.
+    float *ltab = inbuf + M.ltab;
+    if constexpr (LEAN) {
+        const CoarseSteps cs = coarse_steps(COLS * kpt);
+        const ProjK pk = proj_consts();
+        if (wave == 0) {
+            ltab[LT_END] = cs.end;
+            ltab[LT_LSTEP] = cs.lstep;
+            ltab[LT_STEP] = cs.step;
+            ltab[LT_WLF] = pk.wlf;
+            ltab[LT_HLF] = pk.hlf;
+            ltab[LT_KX] = pk.kx;
+            ltab[LT_KY] = pk.ky;
+            ltab[LT_HX] = pk.hx;
+            ltab[LT_HY] = pk.hy;
+        }
+    }
     // the next unit's first tile, claimed by wave 0 (wave-uniform: every value here is scalar)
     auto grab = [&]() -> int {
         const int64_t T = a.n_tiles / upt;
@@ -292,10 +343,17 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     };
     if (wave == 0) *s_next = grab();
     lds_barrier();
-    for (int64_t tile = *s_next; tile < a.n_tiles; tile = *s_next) {
+    // the tile taken from s_next; LEAN: broadcast, so the tile and what derives from it are scalar
+    auto take = [&]() -> int64_t {
+        const int t = *s_next;
+        if constexpr (LEAN) return __builtin_amdgcn_readfirstlane(t);
+        else return t;
+    };
+    for (int64_t tile = take(); tile < a.n_tiles; tile = take()) {
         // this tile within its unit: pass_f = a fine tile of the single-launch march; sub = the
         // tile within its pass (the ray's kpt_t tiles of K_t = 64 kpt_t samples)
-        const int64_t unit = tile / upt;
+        // (LEAN: upt = kpt is 1 or 2, launch_point_mlp: a shift instead of a 64-bit division)
+        const int64_t unit = LEAN ? (upt == 2 ? tile >> 1 : tile) : tile / upt;
         const int s_in = (int)(tile - unit * upt);
         const bool pass_f = single && s_in >= kpt;
         const int sub = pass_f ? s_in - kpt : s_in;
@@ -305,8 +363,16 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
         auto ray_of = [&]() -> int64_t {
             const int *o = MARCH ? march_cfg(a)->order : nullptr;
             if (!o) return unit;
-            const int64_t r = o[unit];
-            return r >= 0 && r < a.n_tiles / upt ? r : unit;
+            if constexpr (LEAN) {
+                // a scalar load; the unit count n_tiles / upt as above, in 32 bits (n_tiles < 2^31,
+                // launch_point_mlp), so the range check is scalar compares
+                const int r = as_const(o)[unit];
+                const int n_units = upt == 2 ? (int)a.n_tiles >> 1 : (int)a.n_tiles;
+                return r >= 0 && r < n_units ? (int64_t)r : unit;
+            } else {
+                const int64_t r = o[unit];
+                return r >= 0 && r < a.n_tiles / upt ? r : unit;
+            }
         };
         // the pass's pack and projected latent (read at use: no per-tile SGPR state)
         auto PK = [&]() -> const float * { return pass_f ? march_cfg(a)->packed_f : a.packed; };
@@ -318,7 +384,12 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
         auto xp_ptr = [&]() { return a.xsum + (int64_t)blockIdx.x * (2 * COLS * H) + wave * (RTW * CT * 256) + opaque_lane(lane) * 4; };
         auto xs_ptr = [&]() { return xp_ptr() + COLS * H; };
 
-        for (int v = 0; v < a.ns; ++v) {
+        // source views (LEAN: one, so no view loop; else read at use like every launch constant)
+        auto NS = [&]() -> int {
+            if constexpr (LEAN) return 1;
+            else return a.ns;
+        };
+        for (int v = 0; v < NS(); ++v) {
             // per view: keeps the feature addresses out of scratch across the GEMMs
             const int tid_t = opaque_lane(tid);
             const int col = tid_t / WAVES, qt = tid_t % WAVES;
@@ -328,7 +399,43 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             // per-view blocks' GEMMs)
             float px, py, pz, dx, dy, dz, zz = 0.f;
             int64_t obj;
-            if (a.render_mode) {
+            // LEAN: the object's camera row and the ray's near / far, fetched with the ray
+            float cam_s[16], nf_s[2];
+            if constexpr (LEAN) {
+                // The unit's ray and the object's camera row by scalar loads: 8 + 16 SGPRs that
+                // every lane's arithmetic below reads as scalar operands (the same fp32 operations
+                // on the same values as the general path's per-lane copies).
+                const int64_t b = ray_of();
+                const int kk = sub * COLS + col;
+                const int kt = COLS * kpt_t;
+                const CFloatPtr rp = as_const(a.rays) + b * 8;
+                float ray[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) ray[i] = rp[i];
+                // one object per launch is the common case: no 64-bit division then (the divisor
+                // through an empty asm: the division's set-up is not hoisted out of the tile loop)
+                int64_t rpo = a.rays_per_obj;
+                asm volatile("" : "+s"(rpo));
+                obj = b < rpo ? 0 : b / rpo;
+                const CFloatPtr cp = as_const(a.cams) + obj * 16;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) cam_s[i] = cp[i];
+                if (march_cfg(a)->sample_coarse) {
+                    const CfgPtr m = march_cfg(a);
+                    const CoarseSteps cs = {ltab[LT_END], ltab[LT_LSTEP], ltab[LT_STEP]};
+                    zz = coarse_z_at(ld_rng(m->u_coarse), b, kt, kk, ray[6], ray[7], m->lindisp != 0, cs);
+                    float *zo = m->z_out;
+                    if (zo && qt == 0) zo[b * kt + kk] = zz;
+                } else {
+                    zz = a.zs[b * kt + kk];
+                }
+                dx = ray[3]; dy = ray[4]; dz = ray[5];
+                px = add_rn(ray[0], mul_rn(zz, dx));
+                py = add_rn(ray[1], mul_rn(zz, dy));
+                pz = add_rn(ray[2], mul_rn(zz, dz));
+                nf_s[0] = ray[6];
+                nf_s[1] = ray[7];
+            } else if (a.render_mode) {
                 // ray b, sample kk of its pass (MARCH: the unit's ray, K = 64 kpt_t)
                 const int64_t b = MARCH ? ray_of() : p / a.K;
                 const int kk = MARCH ? sub * COLS + col : (int)(p - b * a.K);
@@ -363,16 +470,20 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             PT_WAIT();
             PT(gc, 8);
             // ---- per (point, view) geometry (this thread's column) ----------------
-            const float *cam = a.cams + (obj * a.ns + v) * 16;
+            const float *cam_p = a.cams + (obj * NS() + v) * 16;
+            auto cam = [&](int i) -> float {
+                if constexpr (LEAN) return cam_s[i];
+                else return cam_p[i];
+            };
             float xr[3], vd[3], xc[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                const float r0 = cam[3 * i], r1 = cam[3 * i + 1], r2 = cam[3 * i + 2];
+                const float r0 = cam(3 * i), r1 = cam(3 * i + 1), r2 = cam(3 * i + 2);
                 xr[i] = add_rn(add_rn(mul_rn(r0, px), mul_rn(r1, py)), mul_rn(r2, pz));
                 vd[i] = add_rn(add_rn(mul_rn(r0, dx), mul_rn(r1, dy)), mul_rn(r2, dz));
-                xc[i] = add_rn(xr[i], cam[9 + i]);
+                xc[i] = add_rn(xr[i], cam(9 + i));
             }
-            const float fx = cam[12], fy = cam[13], cx = cam[14], cy = cam[15];
+            const float fx = cam(12), fy = cam(13), cx = cam(14), cy = cam(15);
             PT_WAIT();
             PT(gc, 9);
             // features f = FPT qt .. FPT qt + FPT - 1 of [xyz_rot | PE | viewdir_cam | 0]
@@ -381,9 +492,14 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             if (MARCH && qt == 0 && v == 0) {   // for the epilogue
                 if (!pass_f) mreg[sub * COLS + col] = zz;
                 if (col == 0 && sub == 0) {
-                    const float *rr = a.rays + ray_of() * 8;
-                    mnf[0] = rr[6];
-                    mnf[1] = rr[7];
+                    if constexpr (LEAN) {
+                        mnf[0] = nf_s[0];
+                        mnf[1] = nf_s[1];
+                    } else {
+                        const float *rr = a.rays + ray_of() * 8;
+                        mnf[0] = rr[6];
+                        mnf[1] = rr[7];
+                    }
                 }
             }
             {
@@ -405,11 +521,13 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                     }
                     fv[i] = val;
                 }
-                if (a.save && p_raw < a.n_points) {
+                if constexpr (!LEAN) {
+                    if (a.save && p_raw < a.n_points) {
 #pragma unroll
-                    for (int i = 0; i < FPT / 4; ++i)
-                        *reinterpret_cast<f4 *>(sv_f + (v * P + p_raw) * 64 + FPT * qt + 4 * i) =
-                            f4{fv[4 * i], fv[4 * i + 1], fv[4 * i + 2], fv[4 * i + 3]};
+                        for (int i = 0; i < FPT / 4; ++i)
+                            *reinterpret_cast<f4 *>(sv_f + (v * P + p_raw) * 64 + FPT * qt + 4 * i) =
+                                f4{fv[4 * i], fv[4 * i + 1], fv[4 * i + 2], fv[4 * i + 3]};
+                    }
                 }
                 if constexpr (HP) {
                     // column max over its WAVES feature threads (adjacent lanes), scale, split
@@ -438,13 +556,20 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             float w = mul_rn(__fdiv_rn(-xc[1], xc[2]), fy);
             u = add_rn(u, cx);
             w = add_rn(w, cy);
-            const float wlf = (float)a.wl, hlf = (float)a.hl;
-            const float lsx = mul_rn(__fdiv_rn(wlf, sub_rn(wlf, 1.f)), 2.f);
-            const float lsy = mul_rn(__fdiv_rn(hlf, sub_rn(hlf, 1.f)), 2.f);
-            const float gx = sub_rn(mul_rn(u, __fdiv_rn(lsx, a.img_w)), 1.f);
-            const float gy = sub_rn(mul_rn(w, __fdiv_rn(lsy, a.img_h)), 1.f);
-            float ix = mul_rn(add_rn(gx, 1.f), mul_rn(sub_rn(wlf, 1.f), 0.5f));
-            float iy = mul_rn(add_rn(gy, 1.f), mul_rn(sub_rn(hlf, 1.f), 0.5f));
+            // (LEAN: the launch's constants from ltab instead of registers that live across the tile loop)
+            const ProjK pk = [&]() {
+                if constexpr (LEAN) {
+                    const f4 t = *reinterpret_cast<const f4 *>(ltab + LT_WLF);
+                    return ProjK{t.x, t.y, t.z, t.w, ltab[LT_HX], ltab[LT_HY]};
+                } else {
+                    return proj_consts();
+                }
+            }();
+            const float wlf = pk.wlf, hlf = pk.hlf;
+            const float gx = sub_rn(mul_rn(u, pk.kx), 1.f);
+            const float gy = sub_rn(mul_rn(w, pk.ky), 1.f);
+            float ix = mul_rn(add_rn(gx, 1.f), pk.hx);
+            float iy = mul_rn(add_rn(gy, 1.f), pk.hy);
             ix = fminf(fmaxf(ix, 0.f), wlf - 1.f);   // border padding; NaN -> 0
             iy = fminf(fmaxf(iy, 0.f), hlf - 1.f);
             const float x0f = floorf(ix), y0f = floorf(iy);
@@ -457,7 +582,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
             if (y0 + 1 >= a.hl) { wsw = 0.f; wse = 0.f; }
             if (qt == 0) {
                 // per-column gather record: 4 corner offsets (floats from a.latent) + weights
-                const uint32_t base = (uint32_t)((obj * a.ns + v) * (int64_t)a.hl * a.wl * H);
+                const uint32_t base = (uint32_t)((obj * NS() + v) * (int64_t)a.hl * a.wl * H);
                 const uint32_t o00 = base + (uint32_t)(y0 * a.wl + x0) * H, o01 = base + (uint32_t)(y0 * a.wl + x1) * H;
                 const uint32_t o10 = base + (uint32_t)(y1 * a.wl + x0) * H, o11 = base + (uint32_t)(y1 * a.wl + x1) * H;
                 float *t = gtab + col * 8;
@@ -559,7 +684,7 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                                           HP ? &R1 : nullptr);
             }
             // ---- multi-view mean (combine_interleaved: sum over views, then / NS) --
-            if (a.ns > 1) {
+            if constexpr (!LEAN) if (a.ns > 1) {
                 float *xs = xs_ptr();
                 if (v == 0) {
 #pragma unroll
@@ -621,9 +746,11 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
         if constexpr (HP) {
             // no publish: the head reads relu(x) from the accumulators (below); only the
             // activation save of lin_out's input remains
-            if (a.save) {
-                save_relu(x, sv_slot(2 * L.n_blocks), tile, P, wave, lane);
-                save_mask(x, sv_mask + PS * 16 * (2 * L.n_blocks), tile, P, wave, lane);
+            if constexpr (!LEAN) {
+                if (a.save) {
+                    save_relu(x, sv_slot(2 * L.n_blocks), tile, P, wave, lane);
+                    save_mask(x, sv_mask + PS * 16 * (2 * L.n_blocks), tile, P, wave, lane);
+                }
             }
         } else {
             publish_relu(x, tile, 2 * L.n_blocks, 0);
@@ -760,6 +887,13 @@ size_t mlp_xsum_bytes(int ns) {
     return sizeof(float) * (size_t)device_cu_count() * 2 * mlpk::COLS * mlpk::H + 512;
 }
 
+// The lean instantiation (k_point_mlp<.., LEAN>): a process-wide switch, default on, and the
+// kernel the last launch of the process took (pnr_mlp_set_lean / pnr_mlp_last_kernel, pnr_abi.h)
+static std::atomic<int> g_mlp_lean{1};
+static std::atomic<int> g_mlp_last_kernel{PNR_MLP_KERNEL_NONE};
+int mlp_set_lean(int on) { return g_mlp_lean.exchange(on != 0); }
+int mlp_last_kernel() { return g_mlp_last_kernel.load(std::memory_order_relaxed); }
+
 // Launch the fused model over n_points points (render mode if rays != nullptr).
 int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *packed,
                      const float *rays, const float *zs, int K, int64_t rays_per_obj,
@@ -803,7 +937,21 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *pac
     a.tile_ctr = reinterpret_cast<int *>(xsum_ws + (size_t)cus * 2 * mlpk::COLS * mlpk::H);
     if (hipMemsetAsync(a.tile_ctr, 0, 512, st) != hipSuccess) return fail(PNR_ERR_HIP, "point_mlp: hipMemsetAsync failed");
     const int64_t grid = a.n_tiles < cus ? a.n_tiles : cus;
-    const size_t lds = mlpk::lds_bytes(mlpk::fwd_lds(mlpk::is_h(d.precision)), march != nullptr);
+    size_t lds = mlpk::lds_bytes(mlpk::fwd_lds(mlpk::is_h(d.precision)), march != nullptr);
+    // The lean instantiation: a render (rays) of ONE source view on the projected latent by a
+    // per-pass fused march (modes 1 and 2, not the single launch), no activation save, f16x3 or
+    // f16.  Every other descriptor takes the general instantiations below.
+    const bool lean = g_mlp_lean.load(std::memory_order_relaxed) && mlpk::is_h(d.precision) && proj && march &&
+                      !march->single && rays && sc.n_views == 1 && !save;
+    g_mlp_last_kernel.store(lean ? PNR_MLP_KERNEL_LEAN : PNR_MLP_KERNEL_GENERAL, std::memory_order_relaxed);
+    if (lean) {
+        lds = mlpk::lds_bytes_lean(mlpk::fwd_lds(true));   // the march map + the lean table
+        if (d.precision == PNR_PREC_F16)
+            hipLaunchKernelGGL((mlpk::k_point_mlp<1, true, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
+        else
+            hipLaunchKernelGGL((mlpk::k_point_mlp<3, true, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
+        return launch_ok("point_mlp") ? PNR_OK : PNR_ERR_HIP;
+    }
 #define PNR_LAUNCH_MLP(P)                                                                              \
     do {                                                                                               \
         if (proj && march) hipLaunchKernelGGL((mlpk::k_point_mlp<P, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a); \

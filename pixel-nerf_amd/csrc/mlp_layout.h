@@ -116,9 +116,14 @@ __device__ __forceinline__ int scale_exp(float m) {
 // partial maxima and exponents) before petab, prog (Fair's count per wave) in its tail, and hpart
 // (head partials [wave][column][4]) after it.  The fused march appends [mreg, end): the ray's z and
 // head outputs, the epilogue scratch w | cdf | sort, near / far, the fine pack's PE table petab_f.
+// The lean instantiation appends ltab after the march region: launch constants that every tile's
+// features need, computed once per workgroup (LeanTab).
 struct FwdLds {
-    int stg, gtab, cmax, ecol, petab, s_next, prog, hpart, mreg, mscr, mnf, petab_f, end;
+    int stg, gtab, cmax, ecol, petab, s_next, prog, hpart, mreg, mscr, mnf, petab_f, end, ltab;
 };
+// ltab slots (floats): the coarse draw's constants (march_dev.h CoarseSteps), then the projection's
+// (k_point_mlp: the latent size as floats, the pixel -> grid scales and the half extents)
+enum LeanTab { LT_END = 0, LT_LSTEP, LT_STEP, LT_PAD, LT_WLF, LT_HLF, LT_KX, LT_KY, LT_HX, LT_HY, LT_FLOATS = 16 };
 constexpr int IMG_H_FLOATS = PART_HALVES;           // P0 + P1 in floats (two halves per float)
 constexpr int MARCH_BUF_FLOATS = 640;               // z [128] | raw [128][4]
 constexpr FwdLds fwd_lds(bool hp) {
@@ -136,9 +141,11 @@ constexpr FwdLds fwd_lds(bool hp) {
     m.mnf = m.mscr + 3 * 128;
     m.petab_f = m.mnf + 4;
     m.end = m.petab_f + 32;
+    m.ltab = m.end;
     return m;
 }
 constexpr size_t lds_bytes(const FwdLds &m, bool march) { return sizeof(float) * (size_t)(march ? m.end : m.mreg); }
+constexpr size_t lds_bytes_lean(const FwdLds &m) { return sizeof(float) * (size_t)(m.ltab + LT_FLOATS); }
 constexpr int MARCH_LDS_FLOATS = fwd_lds(true).end - fwd_lds(true).mreg;
 
 // k_mlp_bwd: P0 | P1 | cmax | ecol | prog as the forward's fp16 map, no gather records
@@ -162,6 +169,9 @@ static_assert(lds_bytes(fwd_lds(true), true) == 147968 + 4 * MARCH_LDS_FLOATS &&
               fwd_lds(false).end - fwd_lds(false).mreg == MARCH_LDS_FLOATS, "LDS totals with the march region");
 static_assert(lds_bytes(fwd_lds(true), true) <= 160 * 1024 && lds_bytes(fwd_lds(false), true) <= 160 * 1024 &&
               lds_bytes(bwd_lds()) <= 160 * 1024, "one workgroup's LDS");
+static_assert(lds_bytes_lean(fwd_lds(true)) == lds_bytes(fwd_lds(true), true) + 4 * LT_FLOATS &&
+              lds_bytes_lean(fwd_lds(true)) <= 160 * 1024 && fwd_lds(true).ltab % 4 == 0,
+              "the lean table fits beside the fp16 map and the march region, 16-byte aligned");
 static_assert(sizeof(float) * COLS * LDS_LD <= 2 * sizeof(_Float16) * PART_HALVES,
               "the fp32 stage fits in the split image it aliases");
 

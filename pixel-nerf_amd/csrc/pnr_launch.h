@@ -33,6 +33,8 @@ int launch_point_mlp(const pnr_scene &, const pnr_mlp_desc &, const void *, cons
                      const float *, int, int64_t, const float *, const float *, int64_t, int64_t,
                      float *, float *, hipStream_t, float *save = nullptr, const float *proj = nullptr,
                      const MarchCfg *march = nullptr);
+int mlp_set_lean(int on);   // the lean instantiation's process-wide switch (returns the previous setting)
+int mlp_last_kernel();      // PNR_MLP_KERNEL_* of the last launch_point_mlp
 // mlp_bwd.hip
 int launch_mlp_bwd(const pnr_mlp_desc &, const void *, const void *, const float *, const float *, const float *,
                    int64_t, float *, float *, hipStream_t, float *, void *, size_t, int n_views);

@@ -251,6 +251,10 @@ std::vector<at::Tensor> composite_meta(const at::Tensor &z, const at::Tensor &ra
             at::empty({z.size(0)}, o)};
 }
 
+// the lean point-model kernel's process-wide switch and the last launch's kernel (host state only)
+int64_t mlp_set_lean(bool on) { return pnr_mlp_set_lean(on ? 1 : 0); }
+int64_t mlp_last_kernel() { return pnr_mlp_last_kernel(); }
+
 }  // namespace
 
 TORCH_LIBRARY(pnr, m) {
@@ -263,6 +267,9 @@ TORCH_LIBRARY(pnr, m) {
     m.def("point_query(Tensor latent_cl, Tensor cams, int n_obj, int n_views, float image_w, float image_h, "
           "int[] desc, Tensor packed, Tensor? proj, Tensor xyz, Tensor? viewdirs) -> Tensor");
     m.def("composite(Tensor z, Tensor raw, Tensor rays, bool white_bkgd, bool want_weights) -> Tensor[]");
+    // no tensor arguments: registered for every backend
+    m.def("mlp_set_lean(bool on) -> int", &mlp_set_lean);
+    m.def("mlp_last_kernel() -> int", &mlp_last_kernel);
 }
 
 TORCH_LIBRARY_IMPL(pnr, CUDA, m) {

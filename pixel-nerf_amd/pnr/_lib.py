@@ -97,6 +97,8 @@ SIGNATURES = {
                                         ctypes.POINTER(RenderCfg), ctypes.POINTER(RenderOut),
                                         c_vp, c_size, c_vp, ctypes.POINTER(c_vp)]),
     "pnr_render_set_fused": (c_i32, [c_i32]),
+    "pnr_mlp_set_lean": (c_i32, [c_i32]),
+    "pnr_mlp_last_kernel": (c_i32, []),
     "pnr_sample_coarse": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "pnr_sample_fine": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_vp,
                                 c_vp, c_vp, c_i32, c_vp, c_vp]),
@@ -205,6 +207,26 @@ class fused_march:
 
     def __exit__(self, *exc):
         load().pnr_render_set_fused(self.prev)
+        return False
+
+
+# pnr_mlp_last_kernel (PNR_MLP_KERNEL_*)
+MLP_KERNEL_NONE, MLP_KERNEL_GENERAL, MLP_KERNEL_LEAN = 0, 1, 2
+
+
+class lean_mlp:
+    """Context manager: pnr_mlp_set_lean(on) inside, the previous setting restored after.  Off,
+    every point-model launch of the process takes the general kernel (bit-identical outputs)."""
+
+    def __init__(self, on):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        self.prev = load().pnr_mlp_set_lean(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        load().pnr_mlp_set_lean(self.prev)
         return False
 
 
