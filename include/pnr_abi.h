@@ -16,13 +16,15 @@
  * Conventions
  *   - Every pointer is a DEVICE pointer owned by the caller, except the struct
  *     arguments themselves (host memory, read during the call only).
- *   - All tensors are fp32, C-contiguous, row-major, in the shapes given below (one exception:
- *     the float64 `out` of pnr_image_metrics).
+ *   - All tensors are fp32, C-contiguous, row-major, in the shapes given below (exceptions:
+ *     the float64 `out` of pnr_image_metrics and pnr_mesh_distance_reduce, the float64
+ *     `total_area` of pnr_mesh_sample, and the int32 index tensors named as such).
  *   - Calls are asynchronous and stream-ordered on `stream` (a hipStream_t; NULL
  *     = the default stream).  The library never allocates device memory: scratch
  *     comes from a caller-provided workspace sized by the *_workspace_bytes query.
- *     One call waits for its stream before it returns: pnr_mc_emit, which reads the two
- *     counted totals back to check the caller's capacities.  pnr_mc_case_table is host-only.
+ *     Two calls wait for their stream before they return: pnr_mc_emit, which reads the two
+ *     counted totals back to check the caller's capacities, and pnr_mesh_sample, which reads its
+ *     face-index flag and the total area back before it samples.  pnr_mc_case_table is host-only.
  *   - Functions return PNR_OK (0) or a negative pnr_status; pnr_last_error()
  *     returns a thread-local message for the last failing call on that thread.
  *     No C++ exception crosses this boundary.
@@ -625,6 +627,92 @@ size_t pnr_image_metrics_workspace_bytes(int64_t n, int32_t h, int32_t w, int32_
 int pnr_image_metrics(const float *x, const float *y, int64_t n, int32_t h, int32_t w, int32_t c,
                       float data_range, float k1, float k2, void *workspace, size_t workspace_bytes,
                       double *out, pnr_stream_t stream);
+
+/* ---- Mesh metrics (surface sampling, nearest neighbour, score sums; additive in ABI 8) --------
+ * The reference has no counterpart: its eval/eval.py stops at the STL.  These three steps score an
+ * extracted mesh against a ground-truth mesh the way Occupancy Networks' eval_pointcloud does
+ * (Chamfer-L1 / L2, accuracy / completeness, F-score at a distance tau, normal consistency), on
+ * the tensors pnr_mc_emit leaves on the device.
+ *
+ * Surface sampling (pnr_mesh_sample): verts (n_verts, 3) fp32, faces (n_faces, 3) int32.
+ *   Area      area[t] = 0.5 * |(b - a) x (c - a)| of face t = (a, b, c), in fp64 from the fp32
+ *             vertices: the differences, the cross product (x = uy vz - uz vy, ...), the squares
+ *             summed x, y, z, the root and the half, each operation rounded once.
+ *   Indices   a face with an index outside [0, n_verts) is detected in the area pass (its
+ *             vertices are never read) and the call returns PNR_ERR_INVALID before sampling.
+ *   CDF       the inclusive fp64 sum of the areas in a fixed blocked-sequential order.  With
+ *             C = PNR_MESH_SCAN_CHUNK: local[t] = the areas of t's chunk of C faces up to t, added
+ *             one by one from 0; mid[t] = off[chunk] + local[t], off = the totals (local of the
+ *             chunk's last face) of the earlier chunks of t's group of C chunks, added one by one
+ *             from 0; cdf[t] = goff[group] + mid[t], goff = the totals (mid of the group's last
+ *             face) of the earlier groups, added one by one from 0.  The CDF is non-decreasing,
+ *             cdf[t] == cdf[t - 1] bit for bit where area[t] == 0, and total = cdf[n_faces - 1].
+ *             A total that is 0, infinite or NaN returns PNR_ERR_INVALID.
+ *   Draws     sample s uses (u0, u1, u2) = draws k = 0, 1, 2 of ray s of the counter-mode stream
+ *             PNR_RNG_MESH with width 3, offset 0 and key = seed (pnr_rng above): a sample
+ *             depends on (seed, s) only, so the first rows of a longer call equal a shorter one.
+ *   Face      the first t with cdf[t] > (double)u0 * total (binary search): a face of area 0 is
+ *             never picked.
+ *   Point     if u1 + u2 > 1 (the fp32 sum): u1 = 1 - u1, u2 = 1 - u2.  Per coordinate
+ *             (a + u1 * (b - a)) + u2 * (c - a) in fp32, each operation rounded once.
+ *   Normal    the cross product above over its length, in fp64, rounded to fp32: the unit normal
+ *             by the right-hand rule.
+ *   Outputs   points (n, 3) fp32; normals (n, 3) fp32 or NULL; tri (n) int32, the picked face, or
+ *             NULL; total_area: one FLOAT64 on the device.  No atomics: bit-identical from run to
+ *             run.  The call waits for its stream once (it reads the index flag and the total
+ *             before anything is read through a face index), as pnr_mc_emit does.
+ *
+ * Nearest neighbour (pnr_nearest): for every row i of a (n, 3) the nearest row of b (m, 3).
+ *   Distance  dx = a.x - b.x, dy, dz rounded to fp32; d2 = fma(dz, dz, fma(dy, dy, dx * dx)) in
+ *             fp32.  Never the expanded form |a|^2 + |b|^2 - 2 a.b: with D the exact squared
+ *             distance of the fp32 inputs and u = 2^-24, |d2 - D| <= 6 u D whatever the
+ *             coordinates' magnitude.
+ *   Choice    idx[i] = the LOWEST j whose d2 equals the minimum over j of that fp32 d2; d2[i] is
+ *             that minimum.  A comparison with NaN is false: a query none of whose candidates
+ *             compares below +inf returns d2 = +inf, idx = 0.  Deterministic.
+ *   Tiling    a workgroup scores PNR_NEAREST_QUERIES rows of a against one slice of
+ *             PNR_NEAREST_SLICE rows of b, staged PNR_NEAREST_TILE rows at a time; with more than
+ *             one slice the per-slice minima (the workspace) are folded in ascending slice order.
+ *   Limits    n <= 2^31 - 1, m <= 65535 * PNR_NEAREST_SLICE (larger: PNR_ERR_UNSUPPORTED).
+ *
+ * Score sums (pnr_mesh_distance_reduce): from d2_ab / idx_ab (n; a's rows against b) and d2_ba /
+ * idx_ba (m; b's rows against a), the normals of the two clouds (both, or NULL for none) and tau:
+ *   out[0] = sum_i sqrt((double)d2_ab[i])       out[1] = sum_i (double)d2_ab[i]
+ *   out[2] = #{i : sqrt((double)d2_ab[i]) < tau}
+ *   out[3] = sum_i |normals_a[i] . normals_b[idx_ab[i]]|   (0 without normals; an index outside
+ *            [0, m) contributes 0 and is not read through)
+ *   out[4 .. 7] the same four for b -> a.  All fp64, summed in a fixed order (element i by thread
+ *   i mod 1024 in ascending i, the threads by a fixed tree); out[0 .. 3] depend on the a -> b
+ *   inputs only and equal, bit for bit, out[4 .. 7] of a call with the two clouds exchanged.  The
+ *   caller divides by n and m.  One launch, no workspace, no host sync. */
+#define PNR_RNG_MESH 4           /* width 3: (u0, u1, u2) of surface sample `ray` (not a pnr_rng_fill stream) */
+#define PNR_MESH_SCAN_CHUNK 256  /* faces per chunk and chunks per group of the CDF */
+#define PNR_NEAREST_QUERIES 1024 /* rows of a per workgroup (four per lane)          */
+#define PNR_NEAREST_TILE 1024    /* rows of b in LDS at a time                       */
+#define PNR_NEAREST_SLICE 4096   /* rows of b per workgroup                          */
+
+/* Workspace bytes for a mesh of n_faces faces (the CDF, 8 bytes per face, and the group sums); 0 if
+ * n_faces is outside 1 .. 2^31 - 1. */
+size_t pnr_mesh_sample_workspace_bytes(int64_t n_faces);
+
+/* n >= 1 samples of the mesh; n, n_verts <= 2^31 - 1.  workspace 16-byte aligned, total_area
+ * 8-byte aligned. */
+int pnr_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, int64_t n,
+                    uint64_t seed, void *workspace, size_t workspace_bytes, float *points, float *normals,
+                    int32_t *tri, double *total_area, pnr_stream_t stream);
+
+/* Workspace bytes of pnr_nearest (the per-slice minima; 256 unused bytes where b is one slice); 0
+ * for any sizes pnr_nearest would refuse. */
+size_t pnr_nearest_workspace_bytes(int64_t n, int64_t m);
+
+/* d2 (n) fp32, idx (n) int32.  Stream-ordered, no host sync. */
+int pnr_nearest(const float *a, int64_t n, const float *b, int64_t m, void *workspace, size_t workspace_bytes,
+                float *d2, int32_t *idx, pnr_stream_t stream);
+
+/* out: 8 x FLOAT64 on the device, 8-byte aligned.  n, m in 1 .. 2^31 - 1; tau >= 0. */
+int pnr_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64_t n, const float *d2_ba,
+                             const int32_t *idx_ba, int64_t m, const float *normals_a, const float *normals_b,
+                             double tau, double *out, pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

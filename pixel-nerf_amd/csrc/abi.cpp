@@ -1,7 +1,8 @@
 // extern "C" entry points of libpnr.so (declared in include/pnr_abi.h):
 // argument validation, workspace carving and the stream-ordered launch
-// sequence of the coarse + fine ray march.  No allocation, no host sync (pnr_mc_emit alone
-// waits for its stream: mcubes.hip reads the counted totals back to check the capacities).
+// sequence of the coarse + fine ray march.  No allocation, no host sync (two calls wait for
+// their stream: pnr_mc_emit, where mcubes.hip reads the counted totals back to check the
+// capacities, and pnr_mesh_sample, where meshdist.hip reads its index flag and the total area).
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -655,6 +656,51 @@ int pnr_image_metrics(const float *x, const float *y, int64_t n, int32_t h, int3
         return fail(PNR_ERR_INVALID, "pnr_image_metrics: out and workspace must be 8-byte aligned");
     return launch_image_metrics(x, y, n, h, w, c, data_range, k1, k2, workspace, workspace_bytes, out,
                                 (hipStream_t)stream);
+}
+
+size_t pnr_mesh_sample_workspace_bytes(int64_t n_faces) { return mesh_sample_workspace_bytes(n_faces); }
+
+int pnr_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, int64_t n,
+                    uint64_t seed, void *workspace, size_t workspace_bytes, float *points, float *normals,
+                    int32_t *tri, double *total_area, pnr_stream_t stream) {
+    if (n < 1 || n_faces < 1 || n_verts < 1)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_sample: n, n_faces and n_verts must be >= 1");
+    if (!verts || !faces || !points || !total_area || !workspace)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_sample: NULL argument");
+    if (((reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(faces) | reinterpret_cast<uintptr_t>(points) |
+          reinterpret_cast<uintptr_t>(normals) | reinterpret_cast<uintptr_t>(tri)) & 3) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_sample: verts, faces, points, normals and tri must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(total_area) & 7) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_sample: workspace must be 16-byte, total_area 8-byte aligned");
+    return launch_mesh_sample(verts, n_verts, faces, n_faces, n, seed, workspace, workspace_bytes, points, normals, tri,
+                              total_area, (hipStream_t)stream);
+}
+
+size_t pnr_nearest_workspace_bytes(int64_t n, int64_t m) { return nearest_workspace_bytes(n, m); }
+
+int pnr_nearest(const float *a, int64_t n, const float *b, int64_t m, void *workspace, size_t workspace_bytes,
+                float *d2, int32_t *idx, pnr_stream_t stream) {
+    if (n < 1 || m < 1) return fail(PNR_ERR_INVALID, "pnr_nearest: n and m must be >= 1");
+    if (!a || !b || !d2 || !idx) return fail(PNR_ERR_INVALID, "pnr_nearest: NULL argument");
+    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(d2) |
+          reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(workspace)) & 3) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_nearest: a, b, d2, idx and workspace must be 4-byte aligned");
+    return launch_nearest(a, n, b, m, workspace, workspace_bytes, d2, idx, (hipStream_t)stream);
+}
+
+int pnr_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64_t n, const float *d2_ba,
+                             const int32_t *idx_ba, int64_t m, const float *normals_a, const float *normals_b,
+                             double tau, double *out, pnr_stream_t stream) {
+    if (n < 1 || m < 1) return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: n and m must be >= 1");
+    if (!d2_ab || !idx_ab || !d2_ba || !idx_ba || !out)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: NULL argument");
+    if ((normals_a == nullptr) != (normals_b == nullptr))
+        return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: normals of both clouds, or of neither");
+    if (!(tau >= 0.0)) return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: tau must be >= 0");
+    if ((reinterpret_cast<uintptr_t>(out) & 7) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: out must be 8-byte aligned");
+    return launch_mesh_distance_reduce(d2_ab, idx_ab, n, d2_ba, idx_ba, m, normals_a, normals_b, tau, out,
+                                       (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -68,5 +68,13 @@ int launch_mc_emit(const float *, int, int, int, float, void *, size_t, float *,
 size_t image_metrics_workspace_bytes(int64_t, int, int, int);
 int launch_image_metrics(const float *, const float *, int64_t, int, int, int, float, float, float, void *, size_t,
                          double *, hipStream_t);
+// meshdist.hip
+size_t mesh_sample_workspace_bytes(int64_t);
+int launch_mesh_sample(const float *, int64_t, const int32_t *, int64_t, int64_t, uint64_t, void *, size_t, float *,
+                       float *, int32_t *, double *, hipStream_t);
+size_t nearest_workspace_bytes(int64_t, int64_t);
+int launch_nearest(const float *, int64_t, const float *, int64_t, void *, size_t, float *, int32_t *, hipStream_t);
+int launch_mesh_distance_reduce(const float *, const int32_t *, int64_t, const float *, const int32_t *, int64_t,
+                                const float *, const float *, double, double *, hipStream_t);
 
 }  // namespace pnr

@@ -54,6 +54,7 @@ class Rng(ctypes.Structure):
 
 # pnr_rng counter-mode stream ids (PNR_RNG_*)
 RNG_U_COARSE, RNG_U_FINE, RNG_U_FINE_JIT, RNG_N_DEPTH = 0, 1, 2, 3
+RNG_MESH = 4   # PNR_RNG_MESH: the surface-sampling draws of pnr_mesh_sample (not a pnr_rng_fill stream)
 ABI_VERSION = 8
 
 
@@ -144,6 +145,14 @@ SIGNATURES = {
     # per-image MSE / SSIM (csrc/metrics.hip); out is float64
     "pnr_image_metrics_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32]),
     "pnr_image_metrics": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_vp, c_size, c_vp, c_vp]),
+    # mesh metrics (csrc/meshdist.hip); total_area and out are float64, faces / tri / idx int32
+    "pnr_mesh_sample_workspace_bytes": (c_size, [c_i64]),
+    "pnr_mesh_sample": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, ctypes.c_uint64, c_vp, c_size, c_vp, c_vp, c_vp,
+                                c_vp, c_vp]),
+    "pnr_nearest_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pnr_nearest": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_size, c_vp, c_vp, c_vp]),
+    "pnr_mesh_distance_reduce": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, ctypes.c_double, c_vp,
+                                         c_vp]),
 }
 
 # pnr_weight_grad_arith arithmetics (PNR_WGRAD_*, ABI 4)

@@ -17,7 +17,8 @@ import torch
 
 from . import util
 
-__all__ = ["ssim", "psnr_np", "image_metrics", "select_views", "eval_approx"]
+__all__ = ["ssim", "psnr_np", "image_metrics", "select_views", "eval_approx", "mesh_metrics", "sample_mesh_np",
+           "nearest_np", "MESH_METRIC_NAMES"]
 
 
 def psnr_np(pred, target, data_range=1.0):
@@ -145,3 +146,140 @@ def eval_approx(net, renderer, dset, device, source=(64,), batch_size=4, seed=12
     assert ns >= 1
     return {"psnr": psnrs, "ssim": ssims, "mean_psnr": float(np.mean(psnrs)) if psnrs else None,
             "mean_ssim": float(np.mean(ssims)) if ssims else None, "objects": len(psnrs)}
+
+
+# ---- mesh reconstruction metrics (Occupancy Networks' eval_pointcloud) -----------------------------
+MESH_METRIC_NAMES = ("accuracy", "completeness", "chamfer_l1", "chamfer_l2", "precision", "recall", "fscore",
+                     "normals_accuracy", "normals_completeness", "normal_consistency")
+_RNG_MESH = 4   # PNR_RNG_MESH
+
+
+def _mesh_draws(seed, n):
+    """(n, 3) float32: draws 0 .. 2 of rays 0 .. n - 1 of the counter-mode stream PNR_RNG_MESH
+    (include/pnr_abi.h pnr_rng: Philox4x32-10, counter (lo32 e, hi32 e, stream, 0), e = 3 ray + k,
+    key = seed, U[0, 1) = (word 0 >> 8) * 2^-24), what pnr_mesh_sample draws on the device."""
+    mask = np.uint64(0xFFFFFFFF)
+    e = np.arange(3 * n, dtype=np.uint64)
+    c = [e & mask, e >> np.uint64(32), np.full(3 * n, _RNG_MESH, np.uint64), np.zeros(3 * n, np.uint64)]
+    k = [np.uint64(int(seed) & 0xFFFFFFFF), np.uint64((int(seed) >> 32) & 0xFFFFFFFF)]
+    for r in range(10):
+        if r:
+            k = [(k[0] + np.uint64(0x9E3779B9)) & mask, (k[1] + np.uint64(0xBB67AE85)) & mask]
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
+    return ((c[0] >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)).reshape(n, 3)
+
+
+def sample_mesh_np(verts, faces, n, seed=0):
+    """pnr_mesh_sample's rule on the host: ``(points (n, 3) float32, normals (n, 3) float32, tri (n,)
+    int32, total area)``.  Areas in fp64 from the fp32 vertices, their inclusive sum with np.cumsum,
+    the first face whose sum exceeds u0 * total, the fold of (u1, u2) at u1 + u2 > 1, the point
+    a + u1 (b - a) + u2 (c - a) in fp32.  The device's sum runs in another fixed order, so a sample
+    whose target lies within rounding of a face boundary may fall on the neighbouring face there."""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
+    if f.shape[0] == 0 or f.min() < 0 or f.max() >= v.shape[0]:
+        raise ValueError("sample_mesh_np: no faces, or a face index outside [0, %d)" % v.shape[0])
+    a, b, c = (v[f[:, i]] for i in range(3))
+    cr = np.cross(b.astype(np.float64) - a, c.astype(np.float64) - a)
+    ln = np.sqrt(cr[:, 0] * cr[:, 0] + cr[:, 1] * cr[:, 1] + cr[:, 2] * cr[:, 2])
+    cdf = np.cumsum(0.5 * ln)
+    total = float(cdf[-1])
+    if not (total > 0.0 and np.isfinite(total)):
+        raise ValueError("sample_mesh_np: the total area is %r, nothing to sample" % total)
+    u = _mesh_draws(seed, n)
+    tri = np.minimum(np.searchsorted(cdf, u[:, 0].astype(np.float64) * total, side="right"), len(cdf) - 1)
+    u1, u2 = u[:, 1].copy(), u[:, 2].copy()
+    fold = (u1 + u2) > np.float32(1.0)
+    u1[fold], u2[fold] = np.float32(1.0) - u1[fold], np.float32(1.0) - u2[fold]
+    pa, pb, pc = a[tri], b[tri], c[tri]
+    points = (pa + u1[:, None] * (pb - pa)) + u2[:, None] * (pc - pa)
+    normals = (cr[tri] / ln[tri][:, None]).astype(np.float32)
+    return points.astype(np.float32), normals, tri.astype(np.int32), total
+
+
+def nearest_np(a, b, chunk=2048):
+    """(squared distance, index) of the nearest row of b for every row of a, in fp64 on the host:
+    scipy's cKDTree where scipy imports, a chunked brute force otherwise."""
+    a = np.ascontiguousarray(a, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    try:
+        from scipy.spatial import cKDTree
+    except ImportError:
+        cKDTree = None
+    if cKDTree is not None:
+        d, idx = cKDTree(b).query(a)
+        return d * d, idx.astype(np.int64)
+    d2 = np.empty(len(a))
+    idx = np.empty(len(a), np.int64)
+    for i in range(0, len(a), chunk):
+        dd = ((a[i:i + chunk, None, :] - b[None, :, :]) ** 2).sum(-1)
+        idx[i:i + chunk] = dd.argmin(1)
+        d2[i:i + chunk] = dd[np.arange(dd.shape[0]), idx[i:i + chunk]]
+    return d2, idx
+
+
+def _mesh_scores(d2_ab, idx_ab, d2_ba, idx_ba, na, nb, tau):
+    """The ten scores from the two fp64 distance fields (numpy)."""
+    d_ab, d_ba = np.sqrt(d2_ab), np.sqrt(d2_ba)
+    acc, comp = float(d_ab.mean()), float(d_ba.mean())
+    prec, rec = float((d_ab < tau).mean()), float((d_ba < tau).mean())
+    nacc = float(np.abs((na.astype(np.float64) * nb[idx_ab].astype(np.float64)).sum(-1)).mean())
+    ncomp = float(np.abs((nb.astype(np.float64) * na[idx_ba].astype(np.float64)).sum(-1)).mean())
+    return {"accuracy": acc, "completeness": comp, "chamfer_l1": 0.5 * (acc + comp),
+            "chamfer_l2": 0.5 * (float(d2_ab.mean()) + float(d2_ba.mean())), "precision": prec, "recall": rec,
+            "fscore": 2.0 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0, "normals_accuracy": nacc,
+            "normals_completeness": ncomp, "normal_consistency": 0.5 * (nacc + ncomp)}
+
+
+def _empty_mesh_scores():
+    inf = float("inf")
+    out = dict.fromkeys(MESH_METRIC_NAMES, 0.0)
+    out.update(accuracy=inf, completeness=inf, chamfer_l1=inf, chamfer_l2=inf)
+    return out
+
+
+def mesh_metrics(pred, gt, n_samples=100000, tau=0.01, seed=0, backend="auto"):
+    """Scores of a predicted mesh against a ground-truth mesh, each a ``(verts (V, 3), faces (T, 3))``
+    pair of tensors or arrays: ``n_samples`` area-weighted surface samples of each (the predicted
+    mesh drawn with ``seed``, the ground truth with ``seed + 1``), nearest neighbours both ways, and
+    the scores of Occupancy Networks' eval_pointcloud as a dict of floats (MESH_METRIC_NAMES):
+    accuracy / completeness = mean distance pred -> gt / gt -> pred, chamfer_l1 their mean,
+    chamfer_l2 the mean of the two mean SQUARED distances, precision / recall = the share of pred /
+    gt samples nearer than ``tau``, fscore = 2PR / (P + R) (0 where P + R = 0), normals_* the mean
+    |n . n'| with the nearest neighbour.  ``"hip"`` runs pnr.ops.mesh_sample / nearest /
+    mesh_distance on the device the meshes are on (host meshes are moved to the current HIP device)
+    with one read-back; ``"numpy"`` restates the sampling rule on the host and searches with scipy's
+    cKDTree, or a chunked brute force without scipy; ``"auto"`` is hip where a HIP device is present.
+    A predicted mesh without faces is a result, not an error: the four distances are +inf and the
+    other scores 0.  An empty ground truth raises."""
+    if backend == "auto":
+        backend = "hip" if torch.cuda.is_available() else "numpy"
+    if backend not in ("hip", "numpy"):
+        raise ValueError("metrics backend must be 'auto', 'numpy' or 'hip' (got %r)" % (backend,))
+    (pv, pf), (gv, gf) = pred, gt
+    if len(gf) == 0:
+        raise ValueError("mesh_metrics: the ground-truth mesh has no faces")
+    if len(pf) == 0:
+        return _empty_mesh_scores()
+    if backend == "numpy":
+        pv, pf, gv, gf = (t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in (pv, pf, gv, gf))
+        pa, na, _, _ = sample_mesh_np(pv, pf, n_samples, seed)
+        pb, nb, _, _ = sample_mesh_np(gv, gf, n_samples, seed + 1)
+        d2_ab, idx_ab = nearest_np(pa, pb)
+        d2_ba, idx_ba = nearest_np(pb, pa)
+        return _mesh_scores(d2_ab, idx_ab, d2_ba, idx_ba, na, nb, tau)
+    from . import ops
+
+    dev = next((t.device for t in (pv, pf, gv, gf) if torch.is_tensor(t) and t.device.type == "cuda"),
+               torch.device("cuda", torch.cuda.current_device()))
+
+    def on_dev(t, dtype):
+        t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+        return t.to(device=dev, dtype=dtype).reshape(-1, 3)
+
+    pa, na, _, _ = ops.mesh_sample(on_dev(pv, torch.float32), on_dev(pf, torch.int32), n_samples, seed)
+    pb, nb, _, _ = ops.mesh_sample(on_dev(gv, torch.float32), on_dev(gf, torch.int32), n_samples, seed + 1)
+    scores = ops.mesh_distance(pa, na, pb, nb, tau)
+    vals = torch.stack([scores[k] for k in MESH_METRIC_NAMES]).cpu().tolist()
+    return dict(zip(MESH_METRIC_NAMES, vals))

@@ -43,6 +43,32 @@ def read_stl(path):
     return rec["normal"].copy(), rec["tri"].copy()
 
 
+def read_stl_indexed(path):
+    """(verts (3 T, 3) float32, faces (T, 3) int32) of a binary STL: the triangle soup as it stands,
+    ``faces = arange(3 T).reshape(T, 3)`` (no vertex is merged; surface sampling needs none)."""
+    _, tris = read_stl(path)
+    verts = np.ascontiguousarray(tris.reshape(-1, 3), dtype=np.float32)
+    return verts, np.arange(verts.shape[0], dtype=np.int32).reshape(-1, 3)
+
+
+def normalize_bounds(verts, radius=1.0):
+    """Vertices moved so that the centre of their bounding box is the origin and scaled so that the
+    farthest one lies at ``radius``: what the fork's Blender step does to a ground-truth STL before it
+    renders the views.  Works on numpy arrays and torch tensors alike (same type and device back); an
+    empty or single-point set is only centred."""
+    if len(verts) == 0:
+        return verts
+    if hasattr(verts, "detach"):
+        centre = 0.5 * (verts.min(0).values + verts.max(0).values)
+        v = verts - centre
+        far = v.norm(dim=1).max()
+        return v * (radius / far) if float(far) > 0.0 else v
+    v = np.asarray(verts)
+    v = v - 0.5 * (v.min(0) + v.max(0))
+    far = np.sqrt((v.astype(np.float64) ** 2).sum(1)).max()
+    return (v * (radius / far)).astype(v.dtype) if far > 0.0 else v
+
+
 def save_obj(vertices, triangles, path, vert_rgb=None):
     """OBJ with optional vertex colours, the reference's format (recon.py:81-106): ``v`` lines with
     %.4f coordinates (and colours), ``f`` lines with 1-based indices."""

@@ -170,3 +170,145 @@ def image_metrics(x, y, data_range=1.0, k1=0.01, k2=0.03):
                    "pnr_image_metrics")
     psnr = 10.0 * torch.log10(float(data_range) ** 2 / out[:, 0])
     return psnr, out[:, 1]
+
+
+# tile constants of pnr_nearest (PNR_NEAREST_QUERIES / _TILE / _SLICE, include/pnr_abi.h): rows of a
+# per workgroup, rows of b in LDS at a time, rows of b per workgroup; more than NEAREST_SLICE rows of
+# b take the combine pass.  MESH_SCAN_CHUNK (PNR_MESH_SCAN_CHUNK): faces per chunk and chunks per
+# group of pnr_mesh_sample's CDF.
+NEAREST_QUERIES = 1024
+NEAREST_TILE = 1024
+NEAREST_SLICE = 4096
+MESH_SCAN_CHUNK = 256
+
+
+def _cloud(t, name, dtype=torch.float32):
+    if not torch.is_tensor(t):
+        raise TypeError("%s must be a tensor" % name)
+    if t.device.type != "cuda":
+        raise ValueError("pnr: %s must be on a HIP device (got %s); the HIP path has no CPU "
+                         "fallback" % (name, t.device))
+    if t.dtype != dtype:
+        raise ValueError("pnr: %s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("pnr: %s must be (N, 3) (got %s)" % (name, tuple(t.shape)))
+    return t.contiguous()
+
+
+def mesh_sample(verts, faces, n, seed=0, want_normals=True):
+    """``n`` area-weighted samples of the surface of an indexed device mesh (include/pnr_abi.h,
+    "Mesh metrics"; csrc/meshdist.hip): verts (V, 3) float32, faces (T, 3) int32 ->
+    ``(points (n, 3), normals (n, 3) or None, tri (n,) int32, area)``, area a 0-dim float64 device
+    tensor.  Sample s depends on (seed, s) only.  A face index outside [0, V) or a total area of 0
+    raises.  One host sync (the library reads its index flag and the total before it samples)."""
+    verts = _cloud(verts, "verts")
+    faces = _cloud(faces, "faces", torch.int32)
+    if faces.device != verts.device:
+        raise ValueError("pnr: faces is on %s, verts on %s" % (faces.device, verts.device))
+    n, n_v, n_t = int(n), int(verts.shape[0]), int(faces.shape[0])
+    if n < 1:
+        raise ValueError("pnr: n must be >= 1 (got %d)" % n)
+    if n_v < 1 or n_t < 1:
+        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) has no surface to sample" % (n_v, n_t))
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("pnr: seed must be in 0 .. 2^64 - 1 (got %r)" % (seed,))
+    lib = _lib.load()
+    dev = verts.device
+    nbytes = lib.pnr_mesh_sample_workspace_bytes(n_t)
+    if nbytes == 0 or n >= 2 ** 31:
+        raise _lib.PnrError("pnr_mesh_sample: %d faces / %d samples not supported (below 2^31)" % (n_t, n))
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    points = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    normals = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_normals else None
+    tri = torch.empty(n, device=dev, dtype=torch.int32)
+    area = torch.empty((), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mesh_sample(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, n, int(seed), _lib.ptr(ws), nbytes,
+                                       _lib.ptr(points), _lib.ptr(normals), _lib.ptr(tri), _lib.ptr(area),
+                                       _lib.stream_of(dev)), "pnr_mesh_sample")
+    return points, normals, tri, area
+
+
+def nearest(a, b):
+    """For every row of a (n, 3) the nearest row of b (m, 3), both float32 on one device
+    (include/pnr_abi.h, "Mesh metrics"): ``(d2 (n,) float32, idx (n,) int32)``.  d2 is accumulated
+    from the coordinate differences; equal distances resolve to the lowest index.  No host sync."""
+    a = _cloud(a, "a")
+    b = _cloud(b, "b")
+    if b.device != a.device:
+        raise ValueError("pnr: b is on %s, a on %s" % (b.device, a.device))
+    n, m = int(a.shape[0]), int(b.shape[0])
+    if n < 1 or m < 1:
+        raise ValueError("pnr: a and b must hold at least one point each (got %d, %d)" % (n, m))
+    lib = _lib.load()
+    dev = a.device
+    nbytes = lib.pnr_nearest_workspace_bytes(n, m)
+    if nbytes == 0:
+        raise _lib.PnrError("pnr_nearest_workspace_bytes: %d x %d points not supported (n < 2^31, m <= 65535 * %d)"
+                            % (n, m, NEAREST_SLICE))
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    d2 = torch.empty(n, device=dev, dtype=torch.float32)
+    idx = torch.empty(n, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_nearest(_lib.ptr(a), n, _lib.ptr(b), m, _lib.ptr(ws), nbytes, _lib.ptr(d2), _lib.ptr(idx),
+                                   _lib.stream_of(dev)), "pnr_nearest")
+    return d2, idx
+
+
+MESH_DISTANCE_KEYS = ("accuracy", "completeness", "chamfer_l1", "chamfer_l2", "precision", "recall", "fscore",
+                      "normals_accuracy", "normals_completeness", "normal_consistency")
+
+
+def mesh_distance_sums(d2_ab, idx_ab, d2_ba, idx_ba, na, nb, tau):
+    """The eight float64 sums of pnr_mesh_distance_reduce as one device tensor (8,)."""
+    dev = d2_ab.device
+    out = torch.empty(8, device=dev, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mesh_distance_reduce(_lib.ptr(d2_ab), _lib.ptr(idx_ab), int(d2_ab.shape[0]),
+                                                _lib.ptr(d2_ba), _lib.ptr(idx_ba), int(d2_ba.shape[0]), _lib.ptr(na),
+                                                _lib.ptr(nb), float(tau), _lib.ptr(out), _lib.stream_of(dev)),
+                   "pnr_mesh_distance_reduce")
+    return out
+
+
+def mesh_distance(pa, na, pb, nb, tau):
+    """Scores of a predicted cloud pa (n, 3) against a ground-truth cloud pb (m, 3) as Occupancy
+    Networks' eval_pointcloud defines them: a dict of 0-dim float64 device tensors.  accuracy /
+    completeness: mean distance pa -> pb / pb -> pa; chamfer_l1 their mean; chamfer_l2 the mean of
+    the two directions' mean SQUARED distances;
+    precision / recall: the share of pa / pb nearer than ``tau``; fscore = 2PR / (P + R), 0 where
+    P + R = 0; normals_* the mean |n . n'| with the nearest neighbour (na, nb: unit normals of the
+    two clouds, or both None: the normal terms are then 0).  No host sync."""
+    pa = _cloud(pa, "pa")
+    pb = _cloud(pb, "pb")
+    if (na is None) != (nb is None):
+        raise ValueError("pnr: give the normals of both clouds, or of neither")
+    if na is not None:
+        na = _cloud(na, "na")
+        nb = _cloud(nb, "nb")
+        if tuple(na.shape) != tuple(pa.shape) or tuple(nb.shape) != tuple(pb.shape):
+            raise ValueError("pnr: normals must match their points (got %s for %s, %s for %s)" % (
+                tuple(na.shape), tuple(pa.shape), tuple(nb.shape), tuple(pb.shape)))
+    for t, name in ((pb, "pb"), (na, "na"), (nb, "nb")):
+        if t is not None and t.device != pa.device:
+            raise ValueError("pnr: %s is on %s, pa on %s" % (name, t.device, pa.device))
+    if not float(tau) >= 0.0:
+        raise ValueError("pnr: tau must be >= 0 (got %r)" % (tau,))
+    n, m = int(pa.shape[0]), int(pb.shape[0])
+    if n < 1 or m < 1:
+        raise ValueError("pnr: pa and pb must hold at least one point each (got %d, %d)" % (n, m))
+    d2_ab, idx_ab = nearest(pa, pb)
+    d2_ba, idx_ba = nearest(pb, pa)
+    return scores_from_sums(mesh_distance_sums(d2_ab, idx_ab, d2_ba, idx_ba, na, nb, tau), n, m)
+
+
+def scores_from_sums(s, n, m):
+    """The score dict from the eight sums (a device tensor of 8 float64) and the two counts."""
+    acc, acc2, prec, nacc = s[0] / n, s[1] / n, s[2] / n, s[3] / n
+    comp, comp2, rec, ncomp = s[4] / m, s[5] / m, s[6] / m, s[7] / m
+    pr = prec + rec
+    f = torch.where(pr > 0, 2.0 * prec * rec / torch.where(pr > 0, pr, torch.ones_like(pr)), torch.zeros_like(pr))
+    return {"accuracy": acc, "completeness": comp, "chamfer_l1": 0.5 * (acc + comp), "chamfer_l2": 0.5 * (acc2 + comp2),
+            "precision": prec, "recall": rec, "fscore": f, "normals_accuracy": nacc, "normals_completeness": ncomp,
+            "normal_consistency": 0.5 * (nacc + ncomp)}

@@ -18,7 +18,14 @@ outside the grid's range gives a valid empty STL on the device path.  The grid i
 <output>/<object>/<object>_sigma.npy (float32, relu(sigma), [x][y][z] with torch.meshgrid's 'ij'
 order).  In the fork the comparison after the mesh is unreachable (a `continue` follows the
 export); --compare runs it, and --metrics_backend hip scores its views on the device
-(pnr.ops.image_metrics, csrc/metrics.hip) instead of copying them to the host for numpy / scipy."""
+(pnr.ops.image_metrics, csrc/metrics.hip) instead of copying them to the host for numpy / scipy.
+
+--gt_mesh_dir DIR (opt-in; the hip mesh backend only) scores each extracted mesh against
+DIR/<object>.stl while its vertices and faces are still on the device (pnr.evaluate.mesh_metrics:
+Chamfer-L1 / L2, accuracy / completeness, F-score, normal consistency) and writes
+<output>/<object>/mesh_metrics.txt, the file scripts/eval_mesh.py writes from the STL, with that
+script's --normalize / --gt_radius / --n_samples / --tau / --seed.  An object without a ground-truth
+file is skipped with one line on stderr."""
 import argparse
 import os
 import sys
@@ -27,10 +34,12 @@ import traceback
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "pixel-nerf_amd"))
+sys.path.insert(0, os.path.join(REPO, "scripts"))   # eval_mesh, also when this file is loaded by path
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import eval_mesh  # noqa: E402
 from pnr import evaluate, mesh, ops, util  # noqa: E402
 from pnr.conf import parse_file  # noqa: E402
 from pnr.data import get_split_dataset  # noqa: E402
@@ -62,12 +71,12 @@ def _have_skimage():
     return True
 
 
-def export_mesh(sig, thresh, path, backend="auto"):
+def export_mesh(sig, thresh, path, backend="auto", keep=None):
     """The reference's mesh export (eval.py:104-108) of the grid `sig` (a device tensor, or a numpy
     array) to a binary STL at `path`.  Returns (backend used, triangles written, seconds spent
     extracting).  `hip`: pnr.ops.marching_cubes on the device grid + pnr.mesh.write_stl (an empty
     surface writes an empty STL); `skimage`: skimage + trimesh; `auto`: skimage where both import,
-    else hip."""
+    else hip.  `keep`: a dict that receives the device path's "verts" / "faces" tensors."""
     if backend == "auto":
         backend = "skimage" if _have_skimage() else "hip"
     if backend == "skimage":
@@ -90,6 +99,8 @@ def export_mesh(sig, thresh, path, backend="auto"):
     torch.cuda.synchronize(sig.device)
     dt = time.perf_counter() - t0
     mesh.write_stl(path, verts, faces)
+    if keep is not None:
+        keep["verts"], keep["faces"] = verts, faces
     return backend, int(faces.shape[0]), dt
 
 
@@ -113,6 +124,10 @@ def main(argv=None):
     ap.add_argument("--metrics_backend", choices=("numpy", "hip"), default="numpy",
                     help="where --compare scores the views: numpy = on the host, image by image; hip = on the "
                          "device (pnr.ops.image_metrics)")
+    ap.add_argument("--gt_mesh_dir", default=None,
+                    help="ground-truth meshes <object>.stl: score each extracted mesh on the device (needs the "
+                         "hip mesh backend) into <object>/mesh_metrics.txt")
+    eval_mesh.add_mesh_metric_args(ap)
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
     ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
@@ -120,6 +135,8 @@ def main(argv=None):
                          "8-bit step for time")
     args = ap.parse_args(argv)
     args.resume = True
+    if args.gt_mesh_dir is not None and args.mesh_backend == "skimage":
+        ap.error("--gt_mesh_dir scores the device mesh: it needs --mesh_backend hip (or auto without skimage)")
 
     device = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(device)
@@ -161,13 +178,27 @@ def main(argv=None):
             torch.cuda.synchronize(device)
             dt = time.perf_counter() - t0
             # the device extractor reads the grid tensor where it is, before the host copy
+            kept = {}
             backend, n_tri, dt_mesh = export_mesh(sig, args.mesh_thresh, os.path.join(out_dir, name + "_mesh.stl"),
-                                                  args.mesh_backend)
+                                                  args.mesh_backend, keep=kept)
             np.save(os.path.join(out_dir, name + "_sigma.npy"), sig.cpu().numpy())
             print("%s: density grid %d^3 in %.3f s (%.1f M points/s); mesh (%s) %d triangles in %.4f s%s" % (
                 name, args.mesh_res, dt, args.mesh_res ** 3 / dt / 1e6, backend, n_tri, dt_mesh,
                 "" if n_tri else ": threshold %g is outside the grid's range, empty STL written" % args.mesh_thresh),
                 flush=True)
+            if args.gt_mesh_dir is not None and backend != "hip":
+                print("eval: --gt_mesh_dir needs the hip mesh backend (auto chose %s); mesh metrics of %s skipped"
+                      % (backend, name), file=sys.stderr)
+            elif args.gt_mesh_dir is not None:
+                gt_path = os.path.join(args.gt_mesh_dir, name + ".stl")
+                if not os.path.isfile(gt_path):
+                    print("eval: no ground truth %s; mesh metrics of %s skipped" % (gt_path, name), file=sys.stderr)
+                else:   # the device tensors, never the STL just written
+                    pred = (eval_mesh.grid_to_world(kept["verts"], args.mesh_res), kept["faces"])
+                    scores = eval_mesh.score_object(pred, gt_path, os.path.join(out_dir, eval_mesh.OUT_NAME), args,
+                                                    "hip")
+                    print("%s: chamfer_l1 %.6g fscore %.4f normal_consistency %.4f" % (
+                        name, scores["chamfer_l1"], scores["fscore"], scores["normal_consistency"]), flush=True)
             if not args.compare:
                 continue
             tgt = ~src

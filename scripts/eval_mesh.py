@@ -1,0 +1,171 @@
+#!/usr/bin/env python
+"""Mesh reconstruction metrics of the meshes scripts/eval.py writes against the ground-truth STLs
+they were meant to reconstruct (map), then their means over all objects (reduce).  The reference has
+no counterpart: its eval/eval.py stops at the STL.
+
+  python scripts/eval_mesh.py -O <eval output> -G <ground-truth dir> [--mesh_res 256] \
+      [--normalize both|gt|none] [--gt_radius 1.0] [--n_samples 100000] [--tau 0.01] [--seed 0] \
+      [--metrics_backend auto|hip|numpy] [--overwrite] [-R]
+
+Map: every folder ``<object>`` of the output root that holds ``<object>_mesh.stl`` is paired with
+``<ground-truth dir>/<object>.stl``; a missing ground truth skips the object with one line on
+stderr.  eval.py writes vertices in grid index units: they are mapped to the grid's world cube
+[-1, 1]^3 with ``v * 2 / (mesh_res - 1) - 1``.  --normalize both (the default) then brings each mesh
+to the unit sphere by its own bounds (pnr.mesh.normalize_bounds: bounding-box centre to the origin,
+farthest vertex to radius 1), the scale the usual tau = 0.01 is meant for; ``gt`` transforms only the
+ground truth, to --gt_radius (what the fork's Blender step does before it renders the views);
+``none`` compares the two as they stand.  pnr.evaluate.mesh_metrics scores the pair (on the device
+with the hip backend) and ``<object>/mesh_metrics.txt`` gets one ``name value`` line per score.
+
+Reduce: every folder of the output root whose name does not start with "_" and that holds a
+``mesh_metrics.txt`` contributes it; ``all_mesh_metrics.txt`` gets one ``name mean`` line per score
+and a last line ``objects N``.
+"""
+import argparse
+import os
+import os.path as osp
+import sys
+
+REPO = osp.dirname(osp.dirname(osp.abspath(__file__)))
+sys.path.insert(0, osp.join(REPO, "pixel-nerf_amd"))
+
+OUT_NAME = "mesh_metrics.txt"
+
+
+def add_mesh_metric_args(ap):
+    """The flags scripts/eval.py --gt_mesh_dir shares with this script."""
+    ap.add_argument("--normalize", choices=("both", "gt", "none"), default="both",
+                    help="both = each mesh to the unit sphere by its own bounds; gt = only the ground truth, to "
+                         "--gt_radius; none = as they stand")
+    ap.add_argument("--gt_radius", type=float, default=1.0, help="radius of --normalize gt")
+    ap.add_argument("--n_samples", type=int, default=100000, help="surface samples per mesh")
+    ap.add_argument("--tau", type=float, default=0.01, help="distance threshold of precision / recall / F-score")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the surface samples")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="Chamfer / F-score / normal consistency of extracted meshes.")
+    ap.add_argument("--output", "-O", type=str, default="eval", help="Root path of the eval.py output")
+    ap.add_argument("--gt_mesh_dir", "-G", type=str, required=True, help="ground truth, <object>.stl")
+    ap.add_argument("--mesh_res", type=int, default=256, help="the --mesh_res eval.py ran with")
+    add_mesh_metric_args(ap)
+    ap.add_argument("--metrics_backend", choices=("auto", "hip", "numpy"), default="auto",
+                    help="hip = sample and search on the device (pnr.ops), numpy = on the host; auto = hip when a "
+                         "HIP device is present, else numpy")
+    ap.add_argument("--gpu_id", type=int, default=0, help="GPU id (hip backend)")
+    ap.add_argument("--overwrite", action="store_true", help="overwrite existing mesh_metrics.txt")
+    ap.add_argument("--reduce_only", "-R", action="store_true", help="skip the map (per-object metrics)")
+    return ap.parse_args(argv)
+
+
+def grid_to_world(verts, mesh_res):
+    """eval.py's index-unit vertices on the mesh_res^3 grid over [-1, 1]^3."""
+    return verts * (2.0 / (mesh_res - 1)) - 1.0
+
+
+def prepare_pair(pred_verts, gt_verts, args):
+    """The two vertex sets as they are scored (arrays or tensors; the predicted one in world units)."""
+    from pnr import mesh
+
+    if args.normalize == "both":
+        return mesh.normalize_bounds(pred_verts), mesh.normalize_bounds(gt_verts)
+    if args.normalize == "gt":
+        return pred_verts, mesh.normalize_bounds(gt_verts, args.gt_radius)
+    return pred_verts, gt_verts
+
+
+def write_metrics(path, scores):
+    from pnr import evaluate
+
+    with open(path, "w") as f:
+        f.write("".join("{} {!r}\n".format(k, float(scores[k])) for k in evaluate.MESH_METRIC_NAMES))
+
+
+def score_object(pred, gt_path, out_path, args, backend):
+    """pred = (verts in world units, faces); writes out_path, returns the scores."""
+    from pnr import evaluate, mesh
+
+    gv, gf = mesh.read_stl_indexed(gt_path)
+    pv, gv = prepare_pair(pred[0], gv, args)
+    scores = evaluate.mesh_metrics((pv, pred[1]), (gv, gf), n_samples=args.n_samples, tau=args.tau, seed=args.seed,
+                                   backend=backend)
+    write_metrics(out_path, scores)
+    return scores
+
+
+def resolve_backend(args):
+    backend = args.metrics_backend
+    if backend != "numpy":
+        import torch
+
+        if backend == "auto":
+            backend = "hip" if torch.cuda.is_available() else "numpy"
+        if backend == "hip":
+            torch.cuda.set_device(args.gpu_id)
+    return backend
+
+
+def run_map(args):
+    from pnr import mesh
+
+    backend = resolve_backend(args)
+    print("Scoring with the", backend, "backend")
+    done = 0
+    for name in sorted(os.listdir(args.output)):
+        stl = osp.join(args.output, name, name + "_mesh.stl")
+        if name[0] == "_" or not osp.isfile(stl):
+            continue
+        out_path = osp.join(args.output, name, OUT_NAME)
+        if osp.exists(out_path) and not args.overwrite:
+            continue
+        gt_path = osp.join(args.gt_mesh_dir, name + ".stl")
+        if not osp.isfile(gt_path):
+            print("eval_mesh: no ground truth %s; %s skipped" % (gt_path, name), file=sys.stderr)
+            continue
+        pv, pf = mesh.read_stl_indexed(stl)
+        score_object((grid_to_world(pv, args.mesh_res), pf), gt_path, out_path, args, backend)
+        done += 1
+    print(">>> SCORED", done, "OBJECTS")
+
+
+def read_metrics(path):
+    with open(path, "r") as f:
+        return {tok[0]: float(tok[1]) for tok in (line.split() for line in f) if len(tok) == 2}
+
+
+def run_reduce(args):
+    from pnr import evaluate
+
+    folders = sorted(x for x in os.listdir(args.output)
+                     if x[0] != "_" and osp.isfile(osp.join(args.output, x, OUT_NAME)))
+    print(">>> PROCESSING", len(folders), "OBJECTS")
+    if not folders:
+        raise SystemExit("eval_mesh: no %s under %s" % (OUT_NAME, args.output))
+    rows = [read_metrics(osp.join(args.output, x, OUT_NAME)) for x in folders]
+    lines = []
+    for name in evaluate.MESH_METRIC_NAMES:
+        acc = 0.0
+        for row in rows:   # in order from 0.0, divided once
+            acc += row[name]
+        lines.append("{} {!r}".format(name, acc / len(rows)))
+    lines.append("objects {}".format(len(rows)))
+    out_path = osp.join(args.output, "all_mesh_metrics.txt")
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("WROTE", out_path)
+    print("\n".join(lines))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.mesh_res < 2:
+        raise SystemExit("eval_mesh: --mesh_res must be >= 2")
+    if not args.reduce_only:
+        print(">>> Compute")
+        run_map(args)
+    print(">>> Reduce")
+    run_reduce(args)
+
+
+if __name__ == "__main__":
+    main()
