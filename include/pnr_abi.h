@@ -18,7 +18,8 @@
  *     arguments themselves (host memory, read during the call only).
  *   - All tensors are fp32, C-contiguous, row-major, in the shapes given below (exceptions:
  *     the float64 `out` of pnr_image_metrics and pnr_mesh_distance_reduce, the float64
- *     `total_area` of pnr_mesh_sample, and the int32 index tensors named as such).
+ *     `total_area` of pnr_mesh_sample, the float64 `w` of pnr_winding, and the int32 index
+ *     tensors named as such).  The `lo` / `hi` of pnr_box_sample are host arrays.
  *   - Calls are asynchronous and stream-ordered on `stream` (a hipStream_t; NULL
  *     = the default stream).  The library never allocates device memory: scratch
  *     comes from a caller-provided workspace sized by the *_workspace_bytes query.
@@ -713,6 +714,61 @@ int pnr_nearest(const float *a, int64_t n, const float *b, int64_t m, void *work
 int pnr_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64_t n, const float *d2_ba,
                              const int32_t *idx_ba, int64_t m, const float *normals_a, const float *normals_b,
                              double tau, double *out, pnr_stream_t stream);
+
+/* ---- Mesh containment (winding number, box samples; additive in ABI 8) ------------------------
+ * The reference has no counterpart.  Occupancy Networks' third headline score, volumetric IoU, needs
+ * a point-in-mesh test; its own is a compiled ray caster.  Here containment is the generalized
+ * winding number of the indexed mesh pnr_mc_emit leaves on the device: verts (n_verts, 3) fp32,
+ * faces (n_faces, 3) int32, points (n, 3) fp32 -> w (n) FLOAT64.
+ *
+ * Winding number (pnr_winding): w[i] = (sum over faces t of Omega(t, p_i)) / (4 pi).
+ *   Pair      face t = (A, B, C), query p, all in fp32, u . v = fma(u.z, v.z, fma(u.y, v.y, u.x * v.x)):
+ *               a = A - p, b = B - p, c = C - p           each difference rounded once
+ *               la = sqrt(a . a), lb = sqrt(b . b), lc = sqrt(c . c)   correctly rounded roots
+ *               n = b x c: n.x = b.y * c.z - b.z * c.y, ...  two rounded products and one rounded
+ *                          difference per component, NO fma: b == c gives n == 0 exactly
+ *               num = a . n
+ *               den = fma(c . a, lb, fma(b . c, la, fma(a . b, lc, (la * lb) * lc)))
+ *               Omega = 2 * atan2f(num, den); num == 0 and den == 0 (p on a vertex) gives Omega = 0
+ *             (van Oosterom & Strackee 1983).  atan2f is the device math library's, within a few
+ *             ulp; everything else is fixed to the bit.
+ *   Sum       (double)Omega is added in fp64 from 0 in ascending face order within a slice of
+ *             PNR_WINDING_SLICE faces; the per-slice sums (the workspace) are added in ascending
+ *             slice order from slice 0's; the total is divided once by 4 pi (fp64).  No atomics:
+ *             w[i] depends on (p_i, the mesh) only, not on n, the row's position or the run.
+ *   Sign      a closed mesh whose normals point outward by the right-hand rule (pnr_mc_emit's
+ *             orientation for density blobs: towards lower density) gives w = 1 inside, 0 outside.
+ *   Indices   a face with an index outside [0, n_verts) contributes exactly 0 and its vertices are
+ *             never read (pnr_mesh_distance_reduce's convention).  It keeps its place in its slice,
+ *             so w equals, bit for bit, that of the mesh with (0, 0, 0)-indexed faces in their
+ *             places, and that of the mesh without them where it fits one slice or they come last.
+ *   NaN       a query or a vertex with a NaN or infinite coordinate counts as NaN: the w of that
+ *             query, or of every query if a used vertex (one of a face with good indices), is NaN.
+ *   Tiling    a workgroup scores PNR_WINDING_QUERIES queries (two per lane) against one slice,
+ *             staged PNR_WINDING_TILE faces at a time; a partial tile is padded with the triangle
+ *             (0, 0, 0), (0, 0, 0), (0, 0, 0), which contributes exactly 0 like a bad face.
+ *   Limits    n, n_verts <= 2^31 - 1, n_faces <= min(2^31 - 1, 65535 * PNR_WINDING_SLICE) (larger:
+ *             PNR_ERR_UNSUPPORTED).  No host sync, nothing allocated.
+ *
+ * Box samples (pnr_box_sample): points (n, 3) uniform in [lo, hi].  Sample s uses u_k = draw k of
+ * ray s of the counter-mode stream PNR_RNG_VOLUME with width 3, offset 0 and key = seed (pnr_rng
+ * above); coordinate k = fma(u_k, fl(hi_k - lo_k), lo_k), within [lo_k, hi_k].  A sample depends on
+ * (seed, s) only.  lo and hi are HOST arrays of 3, read during the call. */
+#define PNR_RNG_VOLUME 5          /* width 3: (u0, u1, u2) of box sample `ray` (not a pnr_rng_fill stream) */
+#define PNR_WINDING_QUERIES 512   /* queries per workgroup (two per lane)  */
+#define PNR_WINDING_TILE 512      /* faces in LDS at a time                */
+#define PNR_WINDING_SLICE 4096    /* faces per workgroup                   */
+
+/* Workspace bytes of pnr_winding (the per-slice sums, 8 bytes each; 256 unused bytes where the mesh
+ * is one slice); 0 for any sizes pnr_winding would refuse. */
+size_t pnr_winding_workspace_bytes(int64_t n, int64_t n_faces);
+
+/* w (n) FLOAT64, 8-byte aligned like the workspace.  Stream-ordered, no host sync. */
+int pnr_winding(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *points,
+                int64_t n, void *workspace, size_t workspace_bytes, double *w, pnr_stream_t stream);
+
+/* n in 1 .. 2^31 - 1; lo, hi finite with lo_k <= hi_k (else PNR_ERR_INVALID). */
+int pnr_box_sample(const float *lo, const float *hi, int64_t n, uint64_t seed, float *points, pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

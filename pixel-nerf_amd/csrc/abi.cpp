@@ -4,6 +4,7 @@
 // their stream: pnr_mc_emit, where mcubes.hip reads the counted totals back to check the
 // capacities, and pnr_mesh_sample, where meshdist.hip reads its index flag and the total area).
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -701,6 +702,38 @@ int pnr_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64_t 
         return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: out must be 8-byte aligned");
     return launch_mesh_distance_reduce(d2_ab, idx_ab, n, d2_ba, idx_ba, m, normals_a, normals_b, tau, out,
                                        (hipStream_t)stream);
+}
+
+size_t pnr_winding_workspace_bytes(int64_t n, int64_t n_faces) { return winding_workspace_bytes(n, n_faces); }
+
+int pnr_winding(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *points,
+                int64_t n, void *workspace, size_t workspace_bytes, double *w, pnr_stream_t stream) {
+    if (n < 1 || n_faces < 1 || n_verts < 1)
+        return fail(PNR_ERR_INVALID, "pnr_winding: n, n_faces and n_verts must be >= 1");
+    if (!verts || !faces || !points || !w) return fail(PNR_ERR_INVALID, "pnr_winding: NULL argument");
+    if (((reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(faces) | reinterpret_cast<uintptr_t>(points)) &
+         3) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_winding: verts, faces and points must be 4-byte aligned");
+    if (((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(workspace)) & 7) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_winding: w and workspace must be 8-byte aligned");
+    return launch_winding(verts, n_verts, faces, n_faces, points, n, workspace, workspace_bytes, w, (hipStream_t)stream);
+}
+
+int pnr_box_sample(const float *lo, const float *hi, int64_t n, uint64_t seed, float *points, pnr_stream_t stream) {
+    if (n < 1) return fail(PNR_ERR_INVALID, "pnr_box_sample: n must be >= 1");
+    if (!lo || !hi || !points) return fail(PNR_ERR_INVALID, "pnr_box_sample: NULL argument");
+    if (n > 0x7fffffff) return fail(PNR_ERR_UNSUPPORTED, "pnr_box_sample: n above 2^31 - 1");
+    if ((reinterpret_cast<uintptr_t>(points) & 3) != 0)
+        return fail(PNR_ERR_INVALID, "pnr_box_sample: points must be 4-byte aligned");
+    float ext[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || hi[k] < lo[k])
+            return fail(PNR_ERR_INVALID, "pnr_box_sample: bounds must be finite with lo <= hi (axis %d: %g, %g)", k,
+                        (double)lo[k], (double)hi[k]);
+        ext[k] = hi[k] - lo[k];   // rounded once
+        if (!std::isfinite(ext[k])) return fail(PNR_ERR_INVALID, "pnr_box_sample: the extent of axis %d overflows", k);
+    }
+    return launch_box_sample(lo, ext, n, seed, points, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -76,5 +76,10 @@ size_t nearest_workspace_bytes(int64_t, int64_t);
 int launch_nearest(const float *, int64_t, const float *, int64_t, void *, size_t, float *, int32_t *, hipStream_t);
 int launch_mesh_distance_reduce(const float *, const int32_t *, int64_t, const float *, const int32_t *, int64_t,
                                 const float *, const float *, double, double *, hipStream_t);
+// winding.hip
+size_t winding_workspace_bytes(int64_t, int64_t);
+int launch_winding(const float *, int64_t, const int32_t *, int64_t, const float *, int64_t, void *, size_t, double *,
+                   hipStream_t);
+int launch_box_sample(const float[3], const float[3], int64_t, uint64_t, float *, hipStream_t);   // lo, extent
 
 }  // namespace pnr

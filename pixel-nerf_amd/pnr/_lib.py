@@ -55,6 +55,7 @@ class Rng(ctypes.Structure):
 # pnr_rng counter-mode stream ids (PNR_RNG_*)
 RNG_U_COARSE, RNG_U_FINE, RNG_U_FINE_JIT, RNG_N_DEPTH = 0, 1, 2, 3
 RNG_MESH = 4   # PNR_RNG_MESH: the surface-sampling draws of pnr_mesh_sample (not a pnr_rng_fill stream)
+RNG_VOLUME = 5   # PNR_RNG_VOLUME: the box-sample draws of pnr_box_sample (not a pnr_rng_fill stream)
 ABI_VERSION = 8
 
 
@@ -153,6 +154,10 @@ SIGNATURES = {
     "pnr_nearest": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_size, c_vp, c_vp, c_vp]),
     "pnr_mesh_distance_reduce": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, ctypes.c_double, c_vp,
                                          c_vp]),
+    # mesh containment (csrc/winding.hip); w is float64, lo / hi of pnr_box_sample are host float[3]
+    "pnr_winding_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pnr_winding": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_size, c_vp, c_vp]),
+    "pnr_box_sample": (c_i32, [c_vp, c_vp, c_i64, ctypes.c_uint64, c_vp, c_vp]),
 }
 
 # pnr_weight_grad_arith arithmetics (PNR_WGRAD_*, ABI 4)

@@ -18,7 +18,8 @@ import torch
 from . import util
 
 __all__ = ["ssim", "psnr_np", "image_metrics", "select_views", "eval_approx", "mesh_metrics", "sample_mesh_np",
-           "nearest_np", "MESH_METRIC_NAMES"]
+           "nearest_np", "MESH_METRIC_NAMES", "volume_iou", "winding_np", "box_sample_np",
+           "VOLUME_METRIC_NAMES"]
 
 
 def psnr_np(pred, target, data_range=1.0):
@@ -154,20 +155,27 @@ MESH_METRIC_NAMES = ("accuracy", "completeness", "chamfer_l1", "chamfer_l2", "pr
 _RNG_MESH = 4   # PNR_RNG_MESH
 
 
-def _mesh_draws(seed, n):
-    """(n, 3) float32: draws 0 .. 2 of rays 0 .. n - 1 of the counter-mode stream PNR_RNG_MESH
-    (include/pnr_abi.h pnr_rng: Philox4x32-10, counter (lo32 e, hi32 e, stream, 0), e = 3 ray + k,
-    key = seed, U[0, 1) = (word 0 >> 8) * 2^-24), what pnr_mesh_sample draws on the device."""
+def _philox_uniform(seed, stream, count):
+    """(count,) float32: U[0, 1) of elements e = 0 .. count - 1 of a counter-mode stream
+    (include/pnr_abi.h pnr_rng: Philox4x32-10, counter (lo32 e, hi32 e, stream, 0), key = seed,
+    (word 0 >> 8) * 2^-24)."""
     mask = np.uint64(0xFFFFFFFF)
-    e = np.arange(3 * n, dtype=np.uint64)
-    c = [e & mask, e >> np.uint64(32), np.full(3 * n, _RNG_MESH, np.uint64), np.zeros(3 * n, np.uint64)]
+    e = np.arange(count, dtype=np.uint64)
+    c = [e & mask, e >> np.uint64(32), np.full(count, stream, np.uint64), np.zeros(count, np.uint64)]
     k = [np.uint64(int(seed) & 0xFFFFFFFF), np.uint64((int(seed) >> 32) & 0xFFFFFFFF)]
     for r in range(10):
         if r:
             k = [(k[0] + np.uint64(0x9E3779B9)) & mask, (k[1] + np.uint64(0xBB67AE85)) & mask]
         p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
         c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
-    return ((c[0] >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)).reshape(n, 3)
+    return (c[0] >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def _mesh_draws(seed, n):
+    """(n, 3) float32: draws 0 .. 2 of rays 0 .. n - 1 of the counter-mode stream PNR_RNG_MESH
+    (include/pnr_abi.h pnr_rng: Philox4x32-10, counter (lo32 e, hi32 e, stream, 0), e = 3 ray + k,
+    key = seed, U[0, 1) = (word 0 >> 8) * 2^-24), what pnr_mesh_sample draws on the device."""
+    return _philox_uniform(seed, _RNG_MESH, 3 * n).reshape(n, 3)
 
 
 def sample_mesh_np(verts, faces, n, seed=0):
@@ -283,3 +291,143 @@ def mesh_metrics(pred, gt, n_samples=100000, tau=0.01, seed=0, backend="auto"):
     scores = ops.mesh_distance(pa, na, pb, nb, tau)
     vals = torch.stack([scores[k] for k in MESH_METRIC_NAMES]).cpu().tolist()
     return dict(zip(MESH_METRIC_NAMES, vals))
+
+
+# ---- mesh containment and volumetric IoU (Occupancy Networks' third headline score) ----------------
+VOLUME_METRIC_NAMES = ("iou", "volume_pred", "volume_gt", "n_points")
+_RNG_VOLUME = 5   # PNR_RNG_VOLUME
+
+
+def _volume_draws(seed, n):
+    """(n, 3) float32: draws 0 .. 2 of rays 0 .. n - 1 of the counter-mode stream PNR_RNG_VOLUME
+    (width 3, offset 0, key = seed), what pnr_box_sample draws on the device."""
+    return _philox_uniform(seed, _RNG_VOLUME, 3 * n).reshape(n, 3)
+
+
+def box_sample_np(lo, hi, n, seed=0):
+    """pnr_box_sample's rule on the host: (n, 3) float32, coordinate k = u_k * fl(hi_k - lo_k) + lo_k
+    with one rounding.  The product is exact in fp64 and the sum is rounded there before it is
+    rounded to fp32, so a coordinate differs from the device's fma by one ulp where the fp64 sum
+    lands on an fp32 tie (about 2^-29 of the draws)."""
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    ext = (hi - lo).astype(np.float64)
+    return (_volume_draws(seed, n).astype(np.float64) * ext + lo.astype(np.float64)).astype(np.float32)
+
+
+def winding_np(verts, faces, points, chunk=None):
+    """Generalized winding number on the host, (n,) float64: pnr_winding's formula (include/pnr_abi.h,
+    "Mesh containment") in fp64 numpy on the fp32 inputs, ``chunk`` queries at a time (default: about
+    2^21 pairs per step).  A face with an index outside [0, V) contributes 0."""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3).astype(np.float64)
+    f = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3).astype(np.float64)
+    f = f[((f >= 0) & (f < len(v))).all(1)]
+    w = np.zeros(len(p))
+    if len(f) == 0 or len(p) == 0:
+        return w
+    tri = [v[f[:, k], c][None, :] for k in range(3) for c in range(3)]   # Ax Ay Az Bx ... Cz, each (1, T)
+    if chunk is None:
+        chunk = max(1, (1 << 21) // len(f))
+    with np.errstate(invalid="ignore"):
+        for i in range(0, len(p), chunk):
+            q = [p[i:i + chunk, c, None] for c in range(3)]
+            ax, ay, az, bx, by, bz, cx, cy, cz = (tri[3 * k + c] - q[c] for k in range(3) for c in range(3))
+            la = np.sqrt(ax * ax + ay * ay + az * az)
+            lb = np.sqrt(bx * bx + by * by + bz * bz)
+            lc = np.sqrt(cx * cx + cy * cy + cz * cz)
+            num = ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx)
+            den = (la * lb * lc + (ax * bx + ay * by + az * bz) * lc + (bx * cx + by * cy + bz * cz) * la
+                   + (cx * ax + cy * ay + cz * az) * lb)
+            w[i:i + chunk] = (2.0 * np.arctan2(num, den)).sum(-1) / (4.0 * np.pi)   # arctan2(0, 0) = 0
+    return w
+
+
+def _signed_volume_np(v, f):
+    t = np.asarray(v, np.float64)[np.asarray(f, np.int64)]
+    return float(np.einsum("ij,ij->i", t[:, 0], np.cross(t[:, 1], t[:, 2])).sum() / 6.0)
+
+
+def _grown_box(lo, hi, padding):
+    """The sampling box from the fp32 bounds: grown on every side by padding x the largest extent, in
+    fp32 (both backends run this on the host, so their boxes are the same bits)."""
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    pad = np.float32(padding) * (hi - lo).max()
+    return lo - pad, hi + pad
+
+
+def volume_iou(pred, gt, n_points=100000, seed=0, padding=0.05, backend="auto"):
+    """Volumetric IoU of a predicted mesh against a ground-truth mesh, each a ``(verts (V, 3), faces
+    (T, 3))`` pair of tensors or arrays, as Occupancy Networks scores it: ``n_points`` uniform
+    points (pnr_box_sample's draws with ``seed``) in the axis-aligned bounds of both meshes' vertices
+    grown on every side by ``padding`` x the largest extent, each classified against each mesh by its
+    generalized winding number (inside: w > 0.5).  Returns a dict of floats (VOLUME_METRIC_NAMES):
+    ``iou`` = |A and B| / |A or B| from the integer counts (0 where the union is empty),
+    ``volume_pred`` / ``volume_gt`` = the share of points inside times the box's volume, ``n_points``.
+    A mesh whose signed volume (sum of a . (b x c) / 6, fp64) is negative has inward faces: its w is
+    negated before the threshold, so an inside-out STL scores as the solid it bounds.  ``"hip"`` runs
+    pnr.ops.box_sample / mesh_contains on the device the meshes are on (host meshes are moved to the
+    current HIP device) and reads the bounds back once; ``"numpy"`` is the same rule in fp64 on the
+    host (``winding_np``); ``"auto"`` is hip where a HIP device is present.  A predicted mesh without
+    faces is a result: iou 0 and volume_pred 0 (the box is then the ground truth's).  An empty ground
+    truth raises."""
+    if backend == "auto":
+        backend = "hip" if torch.cuda.is_available() else "numpy"
+    if backend not in ("hip", "numpy"):
+        raise ValueError("metrics backend must be 'auto', 'numpy' or 'hip' (got %r)" % (backend,))
+    n_points = int(n_points)
+    if n_points < 1:
+        raise ValueError("volume_iou: n_points must be >= 1 (got %d)" % n_points)
+    (pv, pf), (gv, gf) = pred, gt
+    if len(gf) == 0:
+        raise ValueError("volume_iou: the ground-truth mesh has no faces")
+    empty = len(pf) == 0
+    if backend == "numpy":
+        pv, pf, gv, gf = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (pv, pf, gv, gf))
+        gv = np.ascontiguousarray(gv, np.float32).reshape(-1, 3)
+        both = gv if empty else np.concatenate([np.ascontiguousarray(pv, np.float32).reshape(-1, 3), gv])
+        lo, hi = _grown_box(both.min(0), both.max(0), padding)
+        pts = box_sample_np(lo, hi, n_points, seed)
+
+        def inside(v, f):   # inward faces: the w of the solid they bound
+            w = winding_np(v, f, pts)
+            return (-w if _signed_volume_np(v, f) < 0 else w) > 0.5
+
+        in_g = inside(gv, gf)
+        in_p = np.zeros(n_points, bool) if empty else inside(pv, pf)
+        counts = [int((in_p & in_g).sum()), int((in_p | in_g).sum()), int(in_p.sum()), int(in_g.sum())]
+    else:
+        from . import ops
+
+        dev = next((t.device for t in (pv, pf, gv, gf) if torch.is_tensor(t) and t.device.type == "cuda"),
+                   torch.device("cuda", torch.cuda.current_device()))
+
+        def on_dev(t, dtype):
+            t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+            return t.to(device=dev, dtype=dtype).reshape(-1, 3)
+
+        def signed_volume(v, f):
+            t = v.double()[f.long()]
+            return (t[:, 0] * torch.linalg.cross(t[:, 1], t[:, 2])).sum() / 6.0
+
+        gv, gf = on_dev(gv, torch.float32), on_dev(gf, torch.int32)
+        if empty:
+            both, vol_p = gv, torch.ones((), device=dev, dtype=torch.float64)
+        else:
+            pv, pf = on_dev(pv, torch.float32), on_dev(pf, torch.int32)
+            both, vol_p = torch.cat([pv, gv]), signed_volume(pv, pf)
+        vol_g = signed_volume(gv, gf)
+        # the one read-back before the draws: the fp32 bounds (exact in fp64) and the two signs
+        head = torch.cat([both.min(0).values.double(), both.max(0).values.double(), torch.stack([vol_p, vol_g])]).cpu()
+        lo, hi = _grown_box(head[0:3].numpy().astype(np.float32), head[3:6].numpy().astype(np.float32), padding)
+        pts = ops.box_sample(lo.tolist(), hi.tolist(), n_points, seed, device=dev)
+
+        def inside(v, f, volume):   # inward faces: the w of the solid they bound
+            return ops.mesh_contains(v, f, pts, 0.5) if volume >= 0 else (-ops.winding_number(v, f, pts)) > 0.5
+
+        in_g = inside(gv, gf, float(head[7]))
+        in_p = torch.zeros(n_points, device=dev, dtype=torch.bool) if empty else inside(pv, pf, float(head[6]))
+        counts = torch.stack([(in_p & in_g).sum(), (in_p | in_g).sum(), in_p.sum(), in_g.sum()]).cpu().tolist()
+    inter, union, n_p, n_g = (int(c) for c in counts)
+    box = float(np.prod(hi.astype(np.float64) - lo.astype(np.float64)))
+    return {"iou": inter / union if union else 0.0, "volume_pred": n_p / n_points * box,
+            "volume_gt": n_g / n_points * box, "n_points": float(n_points)}

@@ -312,3 +312,78 @@ def scores_from_sums(s, n, m):
     return {"accuracy": acc, "completeness": comp, "chamfer_l1": 0.5 * (acc + comp), "chamfer_l2": 0.5 * (acc2 + comp2),
             "precision": prec, "recall": rec, "fscore": f, "normals_accuracy": nacc, "normals_completeness": ncomp,
             "normal_consistency": 0.5 * (nacc + ncomp)}
+
+
+# tile constants of pnr_winding (PNR_WINDING_QUERIES / _TILE / _SLICE, include/pnr_abi.h): queries per
+# workgroup, faces in LDS at a time, faces per workgroup; more than WINDING_SLICE faces take the
+# combine pass.
+WINDING_QUERIES = 512
+WINDING_TILE = 512
+WINDING_SLICE = 4096
+
+
+def winding_number(verts, faces, points):
+    """Generalized winding number of an indexed device mesh at every query point (include/pnr_abi.h,
+    "Mesh containment"; csrc/winding.hip): verts (V, 3) float32, faces (T, 3) int32, points (n, 3)
+    float32 -> ``w (n,) float64``.  1 inside and 0 outside a closed mesh with outward faces (the
+    orientation ``marching_cubes`` gives density blobs), a fraction near the holes of an open one.
+    The pairs are scored in fp32 and summed in fp64 in a fixed order: ``w[i]`` depends on
+    ``points[i]`` and the mesh only.  A face with an index outside [0, V) contributes 0; a
+    non-finite query gives NaN.  No host sync."""
+    verts = _cloud(verts, "verts")
+    faces = _cloud(faces, "faces", torch.int32)
+    points = _cloud(points, "points")
+    for t, name in ((faces, "faces"), (points, "points")):
+        if t.device != verts.device:
+            raise ValueError("pnr: %s is on %s, verts on %s" % (name, t.device, verts.device))
+    n, n_v, n_t = int(points.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    if n < 1:
+        raise ValueError("pnr: points must hold at least one point (got %d)" % n)
+    if n_v < 1 or n_t < 1:
+        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) contains nothing" % (n_v, n_t))
+    lib = _lib.load()
+    dev = verts.device
+    nbytes = lib.pnr_winding_workspace_bytes(n, n_t)
+    if nbytes == 0 or n_v >= 2 ** 31:
+        raise _lib.PnrError("pnr_winding_workspace_bytes: %d points x %d faces not supported (n < 2^31, faces <= "
+                            "min(2^31 - 1, 65535 * %d))" % (n, n_t, WINDING_SLICE))
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    w = torch.empty(n, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_winding(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(points), n, _lib.ptr(ws), nbytes,
+                                   _lib.ptr(w), _lib.stream_of(dev)), "pnr_winding")
+    return w
+
+
+def mesh_contains(verts, faces, points, thresh=0.5):
+    """``winding_number(...) > thresh`` as a bool tensor (n,): which points the mesh contains.  A
+    non-finite point is outside."""
+    return winding_number(verts, faces, points) > thresh
+
+
+def box_sample(lo, hi, n, seed=0, device="cuda"):
+    """``n`` points uniform in the box [lo, hi] (two triples of floats) as a float32 device tensor
+    (n, 3): pnr_box_sample (include/pnr_abi.h, "Mesh containment").  Sample s depends on (seed, s)
+    only, so the first rows of a longer call equal a shorter one."""
+    import ctypes
+
+    lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("pnr: lo and hi must be triples (got %d, %d values)" % (len(lo), len(hi)))
+    n = int(n)
+    if n < 1:
+        raise ValueError("pnr: n must be >= 1 (got %d)" % n)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("pnr: seed must be in 0 .. 2^64 - 1 (got %r)" % (seed,))
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("pnr: box_sample draws on a HIP device (got %s); the HIP path has no CPU fallback" % (dev,))
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    c_lo, c_hi = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+    points = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_box_sample(ctypes.cast(c_lo, ctypes.c_void_p), ctypes.cast(c_hi, ctypes.c_void_p), n,
+                                      int(seed), _lib.ptr(points), _lib.stream_of(dev)), "pnr_box_sample")
+    return points

@@ -24,8 +24,10 @@ export); --compare runs it, and --metrics_backend hip scores its views on the de
 DIR/<object>.stl while its vertices and faces are still on the device (pnr.evaluate.mesh_metrics:
 Chamfer-L1 / L2, accuracy / completeness, F-score, normal consistency) and writes
 <output>/<object>/mesh_metrics.txt, the file scripts/eval_mesh.py writes from the STL, with that
-script's --normalize / --gt_radius / --n_samples / --tau / --seed.  An object without a ground-truth
-file is skipped with one line on stderr."""
+script's --normalize / --gt_radius / --n_samples / --tau / --seed.  With --iou (and --n_iou_points)
+the volumetric IoU (pnr.evaluate.volume_iou: winding-number containment, pnr.ops.mesh_contains,
+csrc/winding.hip) is scored from the same device tensors and its lines follow in that file.  An
+object without a ground-truth file is skipped with one line on stderr."""
 import argparse
 import os
 import sys
@@ -197,8 +199,9 @@ def main(argv=None):
                     pred = (eval_mesh.grid_to_world(kept["verts"], args.mesh_res), kept["faces"])
                     scores = eval_mesh.score_object(pred, gt_path, os.path.join(out_dir, eval_mesh.OUT_NAME), args,
                                                     "hip")
-                    print("%s: chamfer_l1 %.6g fscore %.4f normal_consistency %.4f" % (
-                        name, scores["chamfer_l1"], scores["fscore"], scores["normal_consistency"]), flush=True)
+                    print("%s: chamfer_l1 %.6g fscore %.4f normal_consistency %.4f%s" % (
+                        name, scores["chamfer_l1"], scores["fscore"], scores["normal_consistency"],
+                        " iou %.4f" % scores["iou"] if args.iou else ""), flush=True)
             if not args.compare:
                 continue
             tgt = ~src

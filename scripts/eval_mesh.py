@@ -5,7 +5,7 @@ no counterpart: its eval/eval.py stops at the STL.
 
   python scripts/eval_mesh.py -O <eval output> -G <ground-truth dir> [--mesh_res 256] \
       [--normalize both|gt|none] [--gt_radius 1.0] [--n_samples 100000] [--tau 0.01] [--seed 0] \
-      [--metrics_backend auto|hip|numpy] [--overwrite] [-R]
+      [--iou] [--n_iou_points 100000] [--metrics_backend auto|hip|numpy] [--overwrite] [-R]
 
 Map: every folder ``<object>`` of the output root that holds ``<object>_mesh.stl`` is paired with
 ``<ground-truth dir>/<object>.stl``; a missing ground truth skips the object with one line on
@@ -20,6 +20,13 @@ with the hip backend) and ``<object>/mesh_metrics.txt`` gets one ``name value`` 
 Reduce: every folder of the output root whose name does not start with "_" and that holds a
 ``mesh_metrics.txt`` contributes it; ``all_mesh_metrics.txt`` gets one ``name mean`` line per score
 and a last line ``objects N``.
+
+--iou adds the volumetric IoU (pnr.evaluate.volume_iou: --n_iou_points uniform points in the padded
+bounds of the pair as it is scored, drawn with --seed, each classified by its generalized winding
+number against each mesh): ``mesh_metrics.txt`` gets the lines ``iou``, ``volume_pred``,
+``volume_gt`` and ``n_points`` after the others, and the reduce averages them too.  A contributing
+file without them (written by a run without --iou) stops the reduce with the object's name.  Without
+--iou both files are what they were.
 """
 import argparse
 import os
@@ -40,11 +47,14 @@ def add_mesh_metric_args(ap):
     ap.add_argument("--gt_radius", type=float, default=1.0, help="radius of --normalize gt")
     ap.add_argument("--n_samples", type=int, default=100000, help="surface samples per mesh")
     ap.add_argument("--tau", type=float, default=0.01, help="distance threshold of precision / recall / F-score")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the surface samples")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the surface samples (and of the --iou points)")
+    ap.add_argument("--iou", action="store_true",
+                    help="also score the volumetric IoU (winding-number containment) into mesh_metrics.txt")
+    ap.add_argument("--n_iou_points", type=int, default=100000, help="uniform points of --iou")
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description="Chamfer / F-score / normal consistency of extracted meshes.")
+    ap = argparse.ArgumentParser(description="Chamfer / F-score / normal consistency / IoU of extracted meshes.")
     ap.add_argument("--output", "-O", type=str, default="eval", help="Root path of the eval.py output")
     ap.add_argument("--gt_mesh_dir", "-G", type=str, required=True, help="ground truth, <object>.stl")
     ap.add_argument("--mesh_res", type=int, default=256, help="the --mesh_res eval.py ran with")
@@ -74,11 +84,16 @@ def prepare_pair(pred_verts, gt_verts, args):
     return pred_verts, gt_verts
 
 
-def write_metrics(path, scores):
+def metric_names(args):
+    """The lines of a metrics file, in order: the surface scores, then with --iou the volume scores."""
     from pnr import evaluate
 
+    return tuple(evaluate.MESH_METRIC_NAMES) + (tuple(evaluate.VOLUME_METRIC_NAMES) if args.iou else ())
+
+
+def write_metrics(path, scores, names):
     with open(path, "w") as f:
-        f.write("".join("{} {!r}\n".format(k, float(scores[k])) for k in evaluate.MESH_METRIC_NAMES))
+        f.write("".join("{} {!r}\n".format(k, float(scores[k])) for k in names))
 
 
 def score_object(pred, gt_path, out_path, args, backend):
@@ -89,7 +104,10 @@ def score_object(pred, gt_path, out_path, args, backend):
     pv, gv = prepare_pair(pred[0], gv, args)
     scores = evaluate.mesh_metrics((pv, pred[1]), (gv, gf), n_samples=args.n_samples, tau=args.tau, seed=args.seed,
                                    backend=backend)
-    write_metrics(out_path, scores)
+    if args.iou:
+        scores.update(evaluate.volume_iou((pv, pred[1]), (gv, gf), n_points=args.n_iou_points, seed=args.seed,
+                                          backend=backend))
+    write_metrics(out_path, scores, metric_names(args))
     return scores
 
 
@@ -134,16 +152,20 @@ def read_metrics(path):
 
 
 def run_reduce(args):
-    from pnr import evaluate
-
     folders = sorted(x for x in os.listdir(args.output)
                      if x[0] != "_" and osp.isfile(osp.join(args.output, x, OUT_NAME)))
     print(">>> PROCESSING", len(folders), "OBJECTS")
     if not folders:
         raise SystemExit("eval_mesh: no %s under %s" % (OUT_NAME, args.output))
     rows = [read_metrics(osp.join(args.output, x, OUT_NAME)) for x in folders]
+    names = metric_names(args)
+    if args.iou:
+        for x, row in zip(folders, rows):
+            if any(name not in row for name in names):
+                raise SystemExit("eval_mesh: %s of object %s has no volume scores (scored without --iou; run the map "
+                                 "again with --iou --overwrite)" % (OUT_NAME, x))
     lines = []
-    for name in evaluate.MESH_METRIC_NAMES:
+    for name in names:
         acc = 0.0
         for row in rows:   # in order from 0.0, divided once
             acc += row[name]
@@ -160,6 +182,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.mesh_res < 2:
         raise SystemExit("eval_mesh: --mesh_res must be >= 2")
+    if args.n_iou_points < 1:
+        raise SystemExit("eval_mesh: --n_iou_points must be >= 1")
     if not args.reduce_only:
         print(">>> Compute")
         run_map(args)
