@@ -22,13 +22,6 @@ static thread_local char g_err[1024];
 // reads it.
 static std::atomic<int> g_fused_default{2};
 
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
 int fail(int status, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -50,7 +43,18 @@ int device_cu_count() {
     return n;
 }
 
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+// true if any of the pointers has a bit of `mask` (alignment - 1) set; NULL passes
+template <typename... T>
+static bool misaligned(uintptr_t mask, const T *...p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & mask) != 0;
+}
+
+// PNR_ERR_WORKSPACE if the call `who` needs `need` bytes and the caller's workspace is absent or smaller
+static int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, size_t need) {
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(PNR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    return PNR_OK;
+}
 
 static int check_scene(const pnr_scene *sc) {
     if (!sc) return fail(PNR_ERR_INVALID, "scene is NULL");
@@ -60,8 +64,7 @@ static int check_scene(const pnr_scene *sc) {
         return fail(PNR_ERR_INVALID, "latent must be at least 2x2 (align_corners scaling)");
     if (sc->latent_c != 512) return fail(PNR_ERR_UNSUPPORTED, "latent_c must be 512 (got %d)", sc->latent_c);
     if (!(sc->image_w > 0.f) || !(sc->image_h > 0.f)) return fail(PNR_ERR_INVALID, "image size <= 0");
-    if ((reinterpret_cast<uintptr_t>(sc->latent) & 15) != 0)
-        return fail(PNR_ERR_INVALID, "latent must be 16-byte aligned");
+    if (misaligned(15, sc->latent)) return fail(PNR_ERR_INVALID, "latent must be 16-byte aligned");
     if ((int64_t)sc->n_obj * sc->n_views * sc->latent_h * sc->latent_w * sc->latent_c >= (1ll << 32))
         return fail(PNR_ERR_UNSUPPORTED, "latent larger than 2^32 floats (32-bit gather offsets)");
     return PNR_OK;
@@ -98,7 +101,7 @@ int pnr_mlp_pack(const pnr_mlp_weights *w, void *packed, size_t packed_bytes, pn
 
 size_t pnr_point_query_workspace_bytes(const pnr_scene *scene, int64_t n_points) {
     (void)n_points;
-    return scene ? align_up(mlp_xsum_bytes(scene->n_views)) : 0;
+    return scene ? align256(mlp_xsum_bytes(scene->n_views)) : 0;
 }
 
 int pnr_point_query(const pnr_scene *scene, const pnr_mlp_desc *desc, const void *packed,
@@ -119,8 +122,7 @@ int pnr_latent_project(const pnr_scene *scene, const pnr_mlp_weights *w, float *
     if (rc) return rc;
     if (!w || !proj) return fail(PNR_ERR_INVALID, "pnr_latent_project: NULL argument");
     if ((rc = check_desc_for_scene(&w->desc, scene))) return rc;
-    if ((reinterpret_cast<uintptr_t>(proj) & 15) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_latent_project: proj must be 16-byte aligned");
+    if (misaligned(15, proj)) return fail(PNR_ERR_INVALID, "pnr_latent_project: proj must be 16-byte aligned");
     return launch_latent_proj(*scene, *w, proj, proj_bytes, (hipStream_t)stream);
 }
 
@@ -134,14 +136,20 @@ int pnr_point_query_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, const
     if (points_per_obj < 0) return fail(PNR_ERR_INVALID, "points_per_obj < 0");
     const int64_t n_points = points_per_obj * scene->n_obj;
     if (n_points == 0) return PNR_OK;
-    const size_t need = pnr_point_query_workspace_bytes(scene, n_points);
-    if (need && (!workspace || workspace_bytes < need))
-        return fail(PNR_ERR_WORKSPACE, "pnr_point_query: workspace %zu < %zu", workspace_bytes, need);
-    if (proj && (reinterpret_cast<uintptr_t>(proj) & 15) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_point_query_proj: proj must be 16-byte aligned");
-    return launch_point_mlp(*scene, *desc, packed, nullptr, nullptr, 0, 1, xyz, viewdirs,
-                            points_per_obj, n_points, out, static_cast<float *>(workspace),
-                            (hipStream_t)stream, nullptr, proj);
+    if ((rc = check_workspace("pnr_point_query", workspace, workspace_bytes,
+                              pnr_point_query_workspace_bytes(scene, n_points))))
+        return rc;
+    if (misaligned(15, proj)) return fail(PNR_ERR_INVALID, "pnr_point_query_proj: proj must be 16-byte aligned");
+    PointMlpCall c;
+    c.packed = packed;
+    c.proj = proj;
+    c.xyz = xyz;
+    c.dirs = viewdirs;
+    c.points_per_obj = points_per_obj;
+    c.n_points = n_points;
+    c.out = out;
+    c.xsum = static_cast<float *>(workspace);
+    return launch_point_mlp(*scene, *desc, c, (hipStream_t)stream);
 }
 
 size_t pnr_point_save_floats(const pnr_mlp_desc *desc, int64_t n_points) {
@@ -167,11 +175,20 @@ int pnr_render_points(const pnr_scene *scene, const pnr_mlp_desc *desc, const vo
     if (!packed || !out) return fail(PNR_ERR_INVALID, "pnr_render_points: NULL pointer");
     const int64_t n_points = rays->n_rays * k;
     if (n_points == 0) return PNR_OK;
-    const size_t need = pnr_point_query_workspace_bytes(scene, n_points);
-    if (need && (!workspace || workspace_bytes < need))
-        return fail(PNR_ERR_WORKSPACE, "pnr_render_points: workspace %zu < %zu", workspace_bytes, need);
-    return launch_point_mlp(*scene, *desc, packed, rays->rays, z, k, rays->rays_per_obj, nullptr, nullptr, 1,
-                            n_points, out, static_cast<float *>(workspace), (hipStream_t)stream, save);
+    if ((rc = check_workspace("pnr_render_points", workspace, workspace_bytes,
+                              pnr_point_query_workspace_bytes(scene, n_points))))
+        return rc;
+    PointMlpCall c;
+    c.packed = packed;
+    c.rays = rays->rays;
+    c.z = z;
+    c.K = k;
+    c.rays_per_obj = rays->rays_per_obj;
+    c.n_points = n_points;
+    c.out = out;
+    c.save = save;
+    c.xsum = static_cast<float *>(workspace);
+    return launch_point_mlp(*scene, *desc, c, (hipStream_t)stream);
 }
 
 int pnr_composite_backward(const float *z, const float *raw, const float *rays, int64_t n_rays, int32_t k,
@@ -181,8 +198,7 @@ int pnr_composite_backward(const float *z, const float *raw, const float *rays, 
     if (k > 256) return fail(PNR_ERR_UNSUPPORTED, "pnr_composite_backward: k <= 256");
     if (n_rays == 0) return PNR_OK;
     if (!z || !raw || !rays || !d_rgb || !d_raw) return fail(PNR_ERR_INVALID, "pnr_composite_backward: NULL");
-    if (((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(d_raw)) & 15) != 0)
-        return fail(PNR_ERR_INVALID, "raw / d_raw must be 16-byte aligned");
+    if (misaligned(15, raw, d_raw)) return fail(PNR_ERR_INVALID, "raw / d_raw must be 16-byte aligned");
     return launch_composite_bwd(z, raw, rays, n_rays, k, white_bkgd, d_rgb, d_depth, d_weights, d_raw, d_z,
                                 (hipStream_t)stream);
 }
@@ -197,10 +213,8 @@ int pnr_points_input_backward_masked(const pnr_scene *scene, const pnr_mlp_desc 
     if ((rc = check_rays_z(scene, rays, z, k))) return rc;
     if (scene->latent_c != 512) return fail(PNR_ERR_UNSUPPORTED, "input backward: latent_c == 512");
     if (!packed || !d_feat || !d_zlat) return fail(PNR_ERR_INVALID, "pnr_points_input_backward: NULL");
-    return launch_points_in_bwd(rays->rays, z, k, rays->rays_per_obj, rays->n_rays * k, scene->n_views, scene->cams,
-                                scene->latent, scene->latent_h, scene->latent_w, scene->image_w,
-                                scene->image_h, static_cast<const float *>(packed), desc->pe_n, d_feat,
-                                d_zlat, d_latent, d_z, z_mask, (hipStream_t)stream);
+    return launch_points_in_bwd(*scene, *rays, z, k, static_cast<const float *>(packed), desc->pe_n, d_feat, d_zlat,
+                                d_latent, d_z, z_mask, (hipStream_t)stream);
 }
 
 int pnr_points_input_backward(const pnr_scene *scene, const pnr_mlp_desc *desc, const void *packed,
@@ -247,9 +261,7 @@ int pnr_mlp_backward_views(const pnr_mlp_desc *desc, const void *packed, const v
     if (!desc || n_points < 0 || n_views < 1) return fail(PNR_ERR_INVALID, "pnr_mlp_backward: bad arguments");
     if (n_points > 0 && (!packed || !packed_t || !lin_out_w || !save || !d_o || !dy))
         return fail(PNR_ERR_INVALID, "pnr_mlp_backward: NULL argument");
-    if (((reinterpret_cast<uintptr_t>(lin_out_w) | reinterpret_cast<uintptr_t>(save) |
-          reinterpret_cast<uintptr_t>(d_o) | reinterpret_cast<uintptr_t>(dy) |
-          reinterpret_cast<uintptr_t>(d_zlat)) & 15) != 0)
+    if (misaligned(15, lin_out_w, save, d_o, dy, d_zlat))
         return fail(PNR_ERR_INVALID, "pnr_mlp_backward: buffers must be 16-byte aligned");
     return launch_mlp_bwd(*desc, packed, packed_t, lin_out_w, save, d_o, n_points, dy, d_zlat, (hipStream_t)stream,
                           d_bias, workspace, workspace_bytes, n_views);
@@ -282,17 +294,17 @@ static RenderWs render_ws(const pnr_scene *sc, const pnr_render_cfg *cfg, int64_
     RenderWs w;
     const size_t kc = (size_t)cfg->n_coarse, kall = (size_t)(cfg->n_coarse + cfg->n_fine);
     size_t o = 0;
-    w.z_c = o; o += align_up(sizeof(float) * n * kc);
-    w.raw_c = o; o += align_up(sizeof(float) * n * kc * 4);
-    w.w_c = o; o += align_up(sizeof(float) * n * kc);
-    w.z_f = o; o += cfg->n_fine > 0 ? align_up(sizeof(float) * n * kall) : 0;
-    w.raw_f = o; o += cfg->n_fine > 0 ? align_up(sizeof(float) * n * kall * 4) : 0;
-    w.xsum = o; o += align_up(mlp_xsum_bytes(sc->n_views));
+    w.z_c = o; o += align256(sizeof(float) * n * kc);
+    w.raw_c = o; o += align256(sizeof(float) * n * kc * 4);
+    w.w_c = o; o += align256(sizeof(float) * n * kc);
+    w.z_f = o; o += cfg->n_fine > 0 ? align256(sizeof(float) * n * kall) : 0;
+    w.raw_f = o; o += cfg->n_fine > 0 ? align256(sizeof(float) * n * kall * 4) : 0;
+    w.xsum = o; o += align256(mlp_xsum_bytes(sc->n_views));
     // coarse-output reuse when the fine pass runs the coarse MLP (see pnr_render_forward_proj)
     const size_t kf = (size_t)cfg->n_fine;
-    w.origin = o; o += kf > 0 ? align_up(sizeof(int) * n * kall) : 0;
-    w.z_new = o; o += kf > 0 ? align_up(sizeof(float) * n * kf) : 0;
-    w.raw_new = o; o += kf > 0 ? align_up(sizeof(float) * n * kf * 4) : 0;
+    w.origin = o; o += kf > 0 ? align256(sizeof(int) * n * kall) : 0;
+    w.z_new = o; o += kf > 0 ? align256(sizeof(float) * n * kf) : 0;
+    w.raw_new = o; o += kf > 0 ? align256(sizeof(float) * n * kf * 4) : 0;
     w.total = o;
     return w;
 }
@@ -319,11 +331,94 @@ int pnr_render_forward_events(const pnr_scene *scene, const pnr_mlp_desc *desc,
                                    out, workspace, workspace_bytes, stream, events);
 }
 
-int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, const void *coarse_packed,
-                            const void *fine_packed, const float *coarse_proj, const float *fine_proj,
-                            const pnr_rays *rays, const pnr_rng *rng, const pnr_render_cfg *cfg,
-                            const pnr_render_out *out, void *workspace, size_t workspace_bytes,
-                            pnr_stream_t stream, void *const *events) {
+// The route of a render call.  Pure: the march mode, the sample counts, whether the fine pass runs
+// the coarse model on the coarse projection, and whether both projections are present.
+//
+//   route                  coarse pass                              fine pass
+//   single                 k_point_mlp: both passes of every ray in ONE launch
+//   fuse_c                 k_point_mlp (draws z in its prologue,    see below
+//                          composites in its epilogue; fuse_s:
+//                          the epilogue draws the fine samples too)
+//   !fuse_c                sample_coarse, k_point_mlp, composite    see below
+//   kf == 0                                                         none
+//   fuse_f                                                          [sample_fine unless fuse_s], k_point_mlp
+//                                                                   (composites in its epilogue)
+//   reuse                                                           sample_fine, k_point_mlp over the kf new
+//                                                                   samples, merge_raw, composite
+//   otherwise                                                       [sample_fine unless fuse_s], k_point_mlp,
+//                                                                   composite
+struct RenderRoute {
+    bool reuse;    // mlp_fine is None: the fine pass evaluates only its new samples and merges the coarse outputs
+    bool single;   // mode 3: both passes in one launch
+    bool fuse_c;   // the coarse pass is one k_point_mlp launch
+    bool fuse_s;   // ... whose epilogue also draws the fine samples (mode 1)
+    bool fuse_f;   // the fine pass is one k_point_mlp launch
+};
+
+static RenderRoute render_route(int mode, int kc, int kf, bool fine_is_coarse, bool both_proj) {
+    // Fused ray march (default): each pass is ONE k_point_mlp launch whose prologue draws the
+    // coarse depths and whose epilogue composites the ray from LDS (raw never reaches HBM); the
+    // coarse epilogue also draws the fine samples.  Needs rays that are whole 64-point tiles
+    // (K = 64 or 128); other shapes, and the coarse-output reuse below, take the separate
+    // sample / composite kernels, which run the same device code (march_dev.h).
+    const int kall = kc + kf;
+    RenderRoute r;
+    // mlp_fine is None (the coarse pack passed twice, models.py:242-255; eval_approx.py --coarse):
+    // the kc coarse samples re-enter the fine pass with the MLP that already evaluated them, so
+    // only the kf new samples run through it and the coarse outputs are merged in.
+    r.reuse = kf > 0 && fine_is_coarse;
+    const bool fused = mode != 0;
+    r.fuse_c = fused && kc % 64 == 0 && kc <= 128;
+    r.fuse_s = r.fuse_c && mode == 1 && kf > 0 && !r.reuse && kc <= 64 && sort_width(kall) <= 128;
+    r.fuse_f = fused && kf > 0 && !r.reuse && kall % 64 == 0 && kall <= 128;
+    // mode 3: both passes in ONE launch (a ray's coarse tile, then its fine tiles; the fine depths
+    // stay in LDS), for kc = 64 and kc + kf = 128 with both projections; other shapes run mode 2
+    r.single = mode == 3 && r.fuse_c && kf > 0 && !r.reuse && kc == 64 && kall == 128 &&
+               sort_width(kall) <= 128 && both_proj;
+    return r;
+}
+
+// The draws of a render call: injected streams, or Philox counters keyed by {seed, offset}
+struct RenderRng {
+    RngSrc u_coarse, u_fine, u_jit, n_depth;
+};
+
+// MarchCfg of one fused pass: the fields every pass sets ...
+static MarchCfg march_pass(const pnr_render_cfg *cfg, int kpt, float *weights, float *rgb, float *depth) {
+    MarchCfg m = {};
+    m.order = cfg->ray_order;
+    m.kpt = kpt;
+    m.white_bkgd = cfg->white_bkgd;
+    m.weights = weights;
+    m.rgb = rgb;
+    m.depth = depth;
+    return m;
+}
+// ... + the coarse draw in the prologue ...
+static void add_coarse_draw(MarchCfg &m, const pnr_render_cfg *cfg, const RenderRng &g, float *z_out) {
+    m.sample_coarse = 1;
+    m.lindisp = cfg->lindisp;
+    m.u_coarse = g.u_coarse;
+    m.z_out = z_out;
+}
+// ... + the fine draws in the coarse epilogue
+static void add_fine_draw(MarchCfg &m, const pnr_render_cfg *cfg, const RenderRng &g, float *z_fine) {
+    m.kf = cfg->n_fine;
+    m.kfd = cfg->n_fine_depth;
+    m.n_sort = sort_width(cfg->n_coarse + cfg->n_fine);
+    m.depth_std = cfg->depth_std;
+    m.u_fine = g.u_fine;
+    m.u_jit = g.u_jit;
+    m.n_depth = g.n_depth;
+    m.z_fine = z_fine;
+}
+
+// Validation of a render call, up to and including its workspace (n_rays == 0 passes early: the
+// call then launches nothing).
+static int check_render(const pnr_scene *scene, const pnr_mlp_desc *desc, const void *coarse_packed,
+                        const void *fine_packed, const float *coarse_proj, const float *fine_proj,
+                        const pnr_rays *rays, const pnr_rng *rng, const pnr_render_cfg *cfg,
+                        const pnr_render_out *out, const void *workspace, size_t workspace_bytes) {
     int rc = check_scene(scene);
     if (rc) return rc;
     if ((rc = check_desc_for_scene(desc, scene))) return rc;
@@ -333,11 +428,10 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
     if (kc < 1) return fail(PNR_ERR_INVALID, "n_coarse < 1");
     if (cfg->march_mode < -1 || cfg->march_mode > 3)
         return fail(PNR_ERR_INVALID, "march_mode must be -1 (default), 0, 1, 2 or 3 (got %d)", cfg->march_mode);
-    const int mode = cfg->march_mode >= 0 ? cfg->march_mode : g_fused_default.load(std::memory_order_relaxed);
     if (kf < 0 || kfd < 0 || kfd > kf) return fail(PNR_ERR_INVALID, "need 0 <= n_fine_depth <= n_fine");
     if (kc + kf > 1024) return fail(PNR_ERR_UNSUPPORTED, "n_coarse + n_fine must be <= 1024");
     if (kf > 0 && !fine_packed) return fail(PNR_ERR_INVALID, "fine_packed is NULL");
-    if (((reinterpret_cast<uintptr_t>(coarse_proj) | reinterpret_cast<uintptr_t>(fine_proj)) & 15) != 0)
+    if (misaligned(15, coarse_proj, fine_proj))
         return fail(PNR_ERR_INVALID, "latent projections must be 16-byte aligned");
     const int64_t n = rays->n_rays;
     if (n < 0 || !rays->rays) return fail(PNR_ERR_INVALID, "bad rays");
@@ -352,67 +446,59 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
         if (kf - kfd > 0 && (!rng->u_fine || !rng->u_fine_jit)) return fail(PNR_ERR_INVALID, "fine streams NULL");
         if (kfd > 0 && !rng->n_depth) return fail(PNR_ERR_INVALID, "n_depth stream NULL");
     }
-    const RngSrc r_uc{rng->u_coarse, rng->seed, rng->offset, PNR_RNG_U_COARSE};
-    const RngSrc r_uf{rng->u_fine, rng->seed, rng->offset, PNR_RNG_U_FINE};
-    const RngSrc r_uj{rng->u_fine_jit, rng->seed, rng->offset, PNR_RNG_U_FINE_JIT};
-    const RngSrc r_nd{rng->n_depth, rng->seed, rng->offset, PNR_RNG_N_DEPTH};
     if (!out->coarse_rgb || !out->coarse_depth) return fail(PNR_ERR_INVALID, "coarse outputs NULL");
     if (kf > 0 && (!out->fine_rgb || !out->fine_depth)) return fail(PNR_ERR_INVALID, "fine outputs NULL");
+    return check_workspace("pnr_render_forward", workspace, workspace_bytes, render_ws(scene, cfg, n).total);
+}
+
+int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, const void *coarse_packed,
+                            const void *fine_packed, const float *coarse_proj, const float *fine_proj,
+                            const pnr_rays *rays, const pnr_rng *rng, const pnr_render_cfg *cfg,
+                            const pnr_render_out *out, void *workspace, size_t workspace_bytes,
+                            pnr_stream_t stream, void *const *events) {
+    int rc = check_render(scene, desc, coarse_packed, fine_packed, coarse_proj, fine_proj, rays, rng, cfg, out,
+                          workspace, workspace_bytes);
+    if (rc || rays->n_rays == 0) return rc;
+    const int64_t n = rays->n_rays;
+    const int kc = cfg->n_coarse, kf = cfg->n_fine, kfd = cfg->n_fine_depth, kall = kc + kf;
+    const int mode = cfg->march_mode >= 0 ? cfg->march_mode : g_fused_default.load(std::memory_order_relaxed);
+    const RenderRoute route = render_route(mode, kc, kf, fine_packed == coarse_packed && fine_proj == coarse_proj,
+                                           coarse_proj && fine_proj);
+    const RenderRng g{{rng->u_coarse, rng->seed, rng->offset, PNR_RNG_U_COARSE},
+                      {rng->u_fine, rng->seed, rng->offset, PNR_RNG_U_FINE},
+                      {rng->u_fine_jit, rng->seed, rng->offset, PNR_RNG_U_FINE_JIT},
+                      {rng->n_depth, rng->seed, rng->offset, PNR_RNG_N_DEPTH}};
     const RenderWs w = render_ws(scene, cfg, n);
-    if (!workspace || workspace_bytes < w.total)
-        return fail(PNR_ERR_WORKSPACE, "pnr_render_forward: workspace %zu < %zu", workspace_bytes, w.total);
     char *ws = static_cast<char *>(workspace);
     hipStream_t st = (hipStream_t)stream;
     float *zc = out->z_coarse ? out->z_coarse : reinterpret_cast<float *>(ws + w.z_c);
     float *rawc = reinterpret_cast<float *>(ws + w.raw_c);
     float *wc = out->coarse_weights ? out->coarse_weights : reinterpret_cast<float *>(ws + w.w_c);
-    float *xsum = reinterpret_cast<float *>(ws + w.xsum);
-    auto mark = [&](int i) -> int {
+    float *zf = kf > 0 ? (out->z_fine ? out->z_fine : reinterpret_cast<float *>(ws + w.z_f)) : nullptr;
+    auto mark = [&](int i) -> int {   // bench.py reads all seven
         if (!events || !events[i]) return PNR_OK;
         hipError_t e = hipEventRecord((hipEvent_t)events[i], st);
         return e == hipSuccess ? PNR_OK : fail(PNR_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(e));
     };
+    // a k_point_mlp launch of the coarse or the fine model over K samples of every ray at the depths z
+    auto pass_call = [&](bool coarse, const float *z, int K) {
+        PointMlpCall c;
+        c.packed = coarse ? coarse_packed : fine_packed;
+        c.proj = coarse ? coarse_proj : fine_proj;
+        c.rays = rays->rays;
+        c.rays_per_obj = rays->rays_per_obj;
+        c.z = z;
+        c.K = K;
+        c.n_points = n * K;
+        c.xsum = reinterpret_cast<float *>(ws + w.xsum);
+        return c;
+    };
+    auto launch = [&](const PointMlpCall &c) { return launch_point_mlp(*scene, *desc, c, st); };
 
-    // Fused ray march (default): each pass is ONE k_point_mlp launch whose prologue draws the
-    // coarse depths and whose epilogue composites the ray from LDS (raw never reaches HBM); the
-    // coarse epilogue also draws the fine samples.  Needs rays that are whole 64-point tiles
-    // (K = 64 or 128); other shapes, and the coarse-output reuse below, take the separate
-    // sample / composite kernels, which run the same device code (march_dev.h).
-    const int kall = kc + kf;
-    // mlp_fine is None (the coarse pack passed twice, models.py:242-255; eval_approx.py --coarse):
-    // the kc coarse samples re-enter the fine pass with the MLP that already evaluated them, so
-    // only the kf new samples run through it and the coarse outputs are merged in.
-    const bool reuse = kf > 0 && fine_packed == coarse_packed && fine_proj == coarse_proj;
-    const bool fused = mode != 0;
-    const bool fuse_c = fused && kc % 64 == 0 && kc <= 128;
-    const bool fuse_s = fuse_c && mode == 1 && kf > 0 && !reuse &&
-                        kc <= 64 && sort_width(kall) <= 128;
-    const bool fuse_f = fused && kf > 0 && !reuse && kall % 64 == 0 && kall <= 128;
-    float *zf = kf > 0 ? (out->z_fine ? out->z_fine : reinterpret_cast<float *>(ws + w.z_f)) : nullptr;
-    // mode 3: both passes in ONE launch (a ray's coarse tile, then its fine tiles; the fine depths
-    // stay in LDS), for kc = 64 and kc + kf = 128 with both projections; other shapes run mode 2
-    const bool single = mode == 3 && fuse_c && kf > 0 && !reuse && kc == 64 && kall == 128 &&
-                        sort_width(kall) <= 128 && coarse_proj && fine_proj;
-    if (single) {
-        MarchCfg m = {};
-        m.order = cfg->ray_order;
-        m.kpt = 1;
-        m.sample_coarse = 1;
-        m.lindisp = cfg->lindisp;
-        m.white_bkgd = cfg->white_bkgd;
-        m.u_coarse = r_uc;
-        m.z_out = out->z_coarse;
-        m.weights = out->coarse_weights;
-        m.rgb = out->coarse_rgb;
-        m.depth = out->coarse_depth;
-        m.kf = kf;
-        m.kfd = kfd;
-        m.n_sort = sort_width(kall);
-        m.depth_std = cfg->depth_std;
-        m.u_fine = r_uf;
-        m.u_jit = r_uj;
-        m.n_depth = r_nd;
-        m.z_fine = out->z_fine;   // NULL unless the caller wants the fine depths
+    if (route.single) {   // events 0 1 [launch] 2 3 4 5 6
+        MarchCfg m = march_pass(cfg, 1, out->coarse_weights, out->coarse_rgb, out->coarse_depth);
+        add_coarse_draw(m, cfg, g, out->z_coarse);
+        add_fine_draw(m, cfg, g, out->z_fine);   // NULL unless the caller wants the fine depths
         m.single = 1;
         m.kpt_f = kall / 64;
         m.packed_f = static_cast<const float *>(fine_packed);
@@ -420,92 +506,66 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
         m.weights_f = out->fine_weights;
         m.rgb_f = out->fine_rgb;
         m.depth_f = out->fine_depth;
-        if ((rc = mark(0)) || (rc = mark(1))) return rc;
-        if ((rc = launch_point_mlp(*scene, *desc, coarse_packed, rays->rays, zc, kc, rays->rays_per_obj, nullptr,
-                                   nullptr, 1, n * (kc + kall), nullptr, xsum, st, nullptr, coarse_proj, &m)))
-            return rc;
-        for (int i = 2; i <= 6; ++i)
+        PointMlpCall c = pass_call(/*coarse=*/true, zc, kc);
+        c.n_points = n * (kc + kall);
+        c.march = &m;
+        if ((rc = mark(0)) || (rc = mark(1)) || (rc = launch(c))) return rc;
+        for (int i = 2; i < 6; ++i)
             if ((rc = mark(i))) return rc;
-        return PNR_OK;
+        return mark(6);
     }
 
-    // coarse pass (nerf.py:273-276)
+    // coarse pass (nerf.py:273-276); events: fused 0 1 [mlp] 2 3, separate 0 [sample] 1 [mlp] 2 [composite] 3
     if ((rc = mark(0))) return rc;
-    if (fuse_c) {
-        MarchCfg m = {};
-        m.order = cfg->ray_order;
-        m.kpt = kc / 64;
-        m.sample_coarse = 1;
-        m.lindisp = cfg->lindisp;
-        m.white_bkgd = cfg->white_bkgd;
-        m.u_coarse = r_uc;
-        m.z_out = fuse_s ? out->z_coarse : zc;
-        m.weights = fuse_s ? out->coarse_weights : wc;
-        m.rgb = out->coarse_rgb;
-        m.depth = out->coarse_depth;
-        if (fuse_s) {
-            m.kf = kf;
-            m.kfd = kfd;
-            m.n_sort = sort_width(kall);
-            m.depth_std = cfg->depth_std;
-            m.u_fine = r_uf;
-            m.u_jit = r_uj;
-            m.n_depth = r_nd;
-            m.z_fine = zf;
-        }
-        if ((rc = mark(1))) return rc;
-        if ((rc = launch_point_mlp(*scene, *desc, coarse_packed, rays->rays, zc, kc, rays->rays_per_obj, nullptr,
-                                   nullptr, 1, n * kc, reuse ? rawc : nullptr, xsum, st, nullptr, coarse_proj, &m)))
-            return rc;
-        if ((rc = mark(2))) return rc;
+    PointMlpCall c = pass_call(/*coarse=*/true, zc, kc);
+    if (route.fuse_c) {
+        const bool fs = route.fuse_s;
+        MarchCfg m = march_pass(cfg, kc / 64, fs ? out->coarse_weights : wc, out->coarse_rgb, out->coarse_depth);
+        add_coarse_draw(m, cfg, g, fs ? out->z_coarse : zc);
+        if (fs) add_fine_draw(m, cfg, g, zf);
+        if (route.reuse) c.out = rawc;
+        c.march = &m;
+        if ((rc = mark(1)) || (rc = launch(c)) || (rc = mark(2))) return rc;
     } else {
-        if ((rc = launch_sample_coarse(rays->rays, n, kc, r_uc, cfg->lindisp, zc, st))) return rc;
-        if ((rc = mark(1))) return rc;
-        if ((rc = launch_point_mlp(*scene, *desc, coarse_packed, rays->rays, zc, kc, rays->rays_per_obj,
-                                   nullptr, nullptr, 1, n * kc, rawc, xsum, st, nullptr, coarse_proj)))
-            return rc;
-        if ((rc = mark(2))) return rc;
+        c.out = rawc;
+        if ((rc = launch_sample_coarse(rays->rays, n, kc, g.u_coarse, cfg->lindisp, zc, st))) return rc;
+        if ((rc = mark(1)) || (rc = launch(c)) || (rc = mark(2))) return rc;
         if ((rc = launch_composite(zc, rawc, rays->rays, n, kc, cfg->white_bkgd, wc, out->coarse_rgb,
                                    out->coarse_depth, st)))
             return rc;
     }
-    if ((rc = mark(3))) return rc;
-    if (kf == 0) return PNR_OK;
-    // fine pass (nerf.py:284-301)
+    if ((rc = mark(3)) || kf == 0) return rc;
+
+    // fine pass (nerf.py:284-301); events: fused [sample_fine unless fuse_s] 4 [mlp] 5 6,
+    // separate or reuse [sample_fine] 4 [mlp (+ merge)] 5 [composite] 6
     float *rawf = reinterpret_cast<float *>(ws + w.raw_f);
-    int *origin = reuse ? reinterpret_cast<int *>(ws + w.origin) : nullptr;
-    float *z_new = reuse ? reinterpret_cast<float *>(ws + w.z_new) : nullptr;
-    if (!fuse_s && (rc = launch_sample_fine(rays->rays, n, kc, zc, wc, out->coarse_depth, kf, kfd, cfg->depth_std,
-                                            r_uf, r_uj, r_nd, cfg->lindisp, zf, st, origin, z_new)))
+    int *origin = route.reuse ? reinterpret_cast<int *>(ws + w.origin) : nullptr;
+    float *z_new = route.reuse ? reinterpret_cast<float *>(ws + w.z_new) : nullptr;
+    if (!route.fuse_s &&
+        (rc = launch_sample_fine(rays->rays, n, kc, zc, wc, out->coarse_depth, kf, kfd, cfg->depth_std, g.u_fine,
+                                 g.u_jit, g.n_depth, cfg->lindisp, zf, st, origin, z_new)))
         return rc;
     if ((rc = mark(4))) return rc;
-    if (fuse_f) {
-        MarchCfg m = {};
-        m.order = cfg->ray_order;
-        m.kpt = kall / 64;
-        m.white_bkgd = cfg->white_bkgd;
-        m.weights = out->fine_weights;
-        m.rgb = out->fine_rgb;
-        m.depth = out->fine_depth;
-        if ((rc = launch_point_mlp(*scene, *desc, fine_packed, rays->rays, zf, kall, rays->rays_per_obj, nullptr,
-                                   nullptr, 1, n * kall, nullptr, xsum, st, nullptr, fine_proj, &m)))
-            return rc;
-        if ((rc = mark(5))) return rc;
+    if (route.fuse_f) {
+        const MarchCfg m = march_pass(cfg, kall / 64, out->fine_weights, out->fine_rgb, out->fine_depth);
+        c = pass_call(/*coarse=*/false, zf, kall);
+        c.march = &m;
+        if ((rc = launch(c)) || (rc = mark(5))) return rc;
         return mark(6);
     }
-    if (reuse) {
+    if (route.reuse) {
         float *raw_new = reinterpret_cast<float *>(ws + w.raw_new);
-        if ((rc = launch_point_mlp(*scene, *desc, fine_packed, rays->rays, z_new, kf, rays->rays_per_obj,
-                                   nullptr, nullptr, 1, n * kf, raw_new, xsum, st, nullptr, fine_proj)))
-            return rc;
-        if ((rc = launch_merge_raw(origin, rawc, raw_new, n, kc, kf, rawf, st))) return rc;
-    } else if ((rc = launch_point_mlp(*scene, *desc, fine_packed, rays->rays, zf, kall, rays->rays_per_obj,
-                                      nullptr, nullptr, 1, n * kall, rawf, xsum, st, nullptr, fine_proj))) {
-        return rc;
+        c = pass_call(/*coarse=*/false, z_new, kf);
+        c.out = raw_new;
+        if ((rc = launch(c)) || (rc = launch_merge_raw(origin, rawc, raw_new, n, kc, kf, rawf, st))) return rc;
+    } else {
+        c = pass_call(/*coarse=*/false, zf, kall);
+        c.out = rawf;
+        if ((rc = launch(c))) return rc;
     }
     if ((rc = mark(5))) return rc;
-    if ((rc = launch_composite(zf, rawf, rays->rays, n, kall, cfg->white_bkgd, out->fine_weights,
-                               out->fine_rgb, out->fine_depth, st)))
+    if ((rc = launch_composite(zf, rawf, rays->rays, n, kall, cfg->white_bkgd, out->fine_weights, out->fine_rgb,
+                               out->fine_depth, st)))
         return rc;
     return mark(6);
 }
@@ -554,7 +614,7 @@ int pnr_composite(const float *z, const float *raw, const float *rays, int64_t n
     if (n_rays < 0 || k < 1) return fail(PNR_ERR_INVALID, "pnr_composite: bad sizes");
     if (n_rays == 0) return PNR_OK;
     if (!z || !raw || !rays || !rgb || !depth) return fail(PNR_ERR_INVALID, "pnr_composite: NULL");
-    if ((reinterpret_cast<uintptr_t>(raw) & 15) != 0) return fail(PNR_ERR_INVALID, "raw must be 16-byte aligned");
+    if (misaligned(15, raw)) return fail(PNR_ERR_INVALID, "raw must be 16-byte aligned");
     return launch_composite(z, raw, rays, n_rays, k, white_bkgd, weights, rgb, depth, (hipStream_t)stream);
 }
 
@@ -601,7 +661,7 @@ int pnr_gen_rays(const float *poses, int64_t n_images, int32_t pose_rows, int32_
     if (pose_rows != 3 && pose_rows != 4) return fail(PNR_ERR_INVALID, "pnr_gen_rays: pose_rows must be 3 or 4");
     if (n_images == 0 || width == 0 || height == 0) return PNR_OK;
     if (!poses || !rays) return fail(PNR_ERR_INVALID, "pnr_gen_rays: NULL");
-    if ((reinterpret_cast<uintptr_t>(rays) & 15) != 0) return fail(PNR_ERR_INVALID, "rays must be 16-byte aligned");
+    if (misaligned(15, rays)) return fail(PNR_ERR_INVALID, "rays must be 16-byte aligned");
     return launch_gen_rays(poses, n_images, pose_rows, width, height, fx, fy, cx, cy, z_near, z_far, rays,
                            (hipStream_t)stream);
 }
@@ -611,10 +671,9 @@ size_t pnr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) { return mc_wo
 int pnr_mc_count(const float *grid, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace,
                  size_t workspace_bytes, int64_t *counts_dev, pnr_stream_t stream) {
     if (!grid || !workspace || !counts_dev) return fail(PNR_ERR_INVALID, "pnr_mc_count: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(grid) & 3) != 0) return fail(PNR_ERR_INVALID, "pnr_mc_count: grid must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_mc_count: workspace must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(counts_dev) & 7) != 0)
+    if (misaligned(3, grid)) return fail(PNR_ERR_INVALID, "pnr_mc_count: grid must be 4-byte aligned");
+    if (misaligned(15, workspace)) return fail(PNR_ERR_INVALID, "pnr_mc_count: workspace must be 16-byte aligned");
+    if (misaligned(7, counts_dev))
         return fail(PNR_ERR_INVALID, "pnr_mc_count: counts_dev must be 8-byte aligned");
     return launch_mc_count(grid, nx, ny, nz, level, workspace, workspace_bytes, counts_dev, (hipStream_t)stream);
 }
@@ -627,11 +686,9 @@ int pnr_mc_emit(const float *grid, int32_t nx, int32_t ny, int32_t nz, float lev
         return fail(PNR_ERR_INVALID, "pnr_mc_emit: capacities must be in 0 .. 2^31 - 1 (int32 vertex indices)");
     if ((verts_cap > 0 && !verts) || (faces_cap > 0 && !faces))
         return fail(PNR_ERR_INVALID, "pnr_mc_emit: NULL output with a non-zero capacity");
-    if ((reinterpret_cast<uintptr_t>(grid) & 3) != 0 || (reinterpret_cast<uintptr_t>(verts) & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(faces) & 3) != 0)
+    if (misaligned(3, grid, verts, faces))
         return fail(PNR_ERR_INVALID, "pnr_mc_emit: grid, verts and faces must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_mc_emit: workspace must be 16-byte aligned");
+    if (misaligned(15, workspace)) return fail(PNR_ERR_INVALID, "pnr_mc_emit: workspace must be 16-byte aligned");
     return launch_mc_emit(grid, nx, ny, nz, level, workspace, workspace_bytes, verts, verts_cap, faces, faces_cap,
                           (hipStream_t)stream);
 }
@@ -651,9 +708,8 @@ int pnr_image_metrics(const float *x, const float *y, int64_t n, int32_t h, int3
                       pnr_stream_t stream) {
     if (!x || !y || !out) return fail(PNR_ERR_INVALID, "pnr_image_metrics: NULL argument");
     if (!(data_range > 0.f)) return fail(PNR_ERR_INVALID, "pnr_image_metrics: data_range must be > 0");
-    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 3) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_image_metrics: x and y must be 4-byte aligned");
-    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7) != 0)
+    if (misaligned(3, x, y)) return fail(PNR_ERR_INVALID, "pnr_image_metrics: x and y must be 4-byte aligned");
+    if (misaligned(7, out, workspace))
         return fail(PNR_ERR_INVALID, "pnr_image_metrics: out and workspace must be 8-byte aligned");
     return launch_image_metrics(x, y, n, h, w, c, data_range, k1, k2, workspace, workspace_bytes, out,
                                 (hipStream_t)stream);
@@ -668,10 +724,9 @@ int pnr_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces, i
         return fail(PNR_ERR_INVALID, "pnr_mesh_sample: n, n_faces and n_verts must be >= 1");
     if (!verts || !faces || !points || !total_area || !workspace)
         return fail(PNR_ERR_INVALID, "pnr_mesh_sample: NULL argument");
-    if (((reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(faces) | reinterpret_cast<uintptr_t>(points) |
-          reinterpret_cast<uintptr_t>(normals) | reinterpret_cast<uintptr_t>(tri)) & 3) != 0)
+    if (misaligned(3, verts, faces, points, normals, tri))
         return fail(PNR_ERR_INVALID, "pnr_mesh_sample: verts, faces, points, normals and tri must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(total_area) & 7) != 0)
+    if (misaligned(15, workspace) || misaligned(7, total_area))
         return fail(PNR_ERR_INVALID, "pnr_mesh_sample: workspace must be 16-byte, total_area 8-byte aligned");
     return launch_mesh_sample(verts, n_verts, faces, n_faces, n, seed, workspace, workspace_bytes, points, normals, tri,
                               total_area, (hipStream_t)stream);
@@ -683,8 +738,7 @@ int pnr_nearest(const float *a, int64_t n, const float *b, int64_t m, void *work
                 float *d2, int32_t *idx, pnr_stream_t stream) {
     if (n < 1 || m < 1) return fail(PNR_ERR_INVALID, "pnr_nearest: n and m must be >= 1");
     if (!a || !b || !d2 || !idx) return fail(PNR_ERR_INVALID, "pnr_nearest: NULL argument");
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(d2) |
-          reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(workspace)) & 3) != 0)
+    if (misaligned(3, a, b, d2, idx, workspace))
         return fail(PNR_ERR_INVALID, "pnr_nearest: a, b, d2, idx and workspace must be 4-byte aligned");
     return launch_nearest(a, n, b, m, workspace, workspace_bytes, d2, idx, (hipStream_t)stream);
 }
@@ -698,8 +752,7 @@ int pnr_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64_t 
     if ((normals_a == nullptr) != (normals_b == nullptr))
         return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: normals of both clouds, or of neither");
     if (!(tau >= 0.0)) return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: tau must be >= 0");
-    if ((reinterpret_cast<uintptr_t>(out) & 7) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: out must be 8-byte aligned");
+    if (misaligned(7, out)) return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: out must be 8-byte aligned");
     return launch_mesh_distance_reduce(d2_ab, idx_ab, n, d2_ba, idx_ba, m, normals_a, normals_b, tau, out,
                                        (hipStream_t)stream);
 }
@@ -711,10 +764,9 @@ int pnr_winding(const float *verts, int64_t n_verts, const int32_t *faces, int64
     if (n < 1 || n_faces < 1 || n_verts < 1)
         return fail(PNR_ERR_INVALID, "pnr_winding: n, n_faces and n_verts must be >= 1");
     if (!verts || !faces || !points || !w) return fail(PNR_ERR_INVALID, "pnr_winding: NULL argument");
-    if (((reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(faces) | reinterpret_cast<uintptr_t>(points)) &
-         3) != 0)
+    if (misaligned(3, verts, faces, points))
         return fail(PNR_ERR_INVALID, "pnr_winding: verts, faces and points must be 4-byte aligned");
-    if (((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(workspace)) & 7) != 0)
+    if (misaligned(7, w, workspace))
         return fail(PNR_ERR_INVALID, "pnr_winding: w and workspace must be 8-byte aligned");
     return launch_winding(verts, n_verts, faces, n_faces, points, n, workspace, workspace_bytes, w, (hipStream_t)stream);
 }
@@ -723,8 +775,7 @@ int pnr_box_sample(const float *lo, const float *hi, int64_t n, uint64_t seed, f
     if (n < 1) return fail(PNR_ERR_INVALID, "pnr_box_sample: n must be >= 1");
     if (!lo || !hi || !points) return fail(PNR_ERR_INVALID, "pnr_box_sample: NULL argument");
     if (n > 0x7fffffff) return fail(PNR_ERR_UNSUPPORTED, "pnr_box_sample: n above 2^31 - 1");
-    if ((reinterpret_cast<uintptr_t>(points) & 3) != 0)
-        return fail(PNR_ERR_INVALID, "pnr_box_sample: points must be 4-byte aligned");
+    if (misaligned(3, points)) return fail(PNR_ERR_INVALID, "pnr_box_sample: points must be 4-byte aligned");
     float ext[3];
     for (int k = 0; k < 3; ++k) {
         if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || hi[k] < lo[k])

@@ -270,8 +270,6 @@ struct Plan {
     bool empty;                                 // a dimension of 1: no cells
 };
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static int plan(int nx, int ny, int nz, Plan &pl) {
     if (nx < 1 || ny < 1 || nz < 1) return fail(PNR_ERR_INVALID, "marching cubes: grid dimensions must be >= 1");
     if (nx > kMaxDim || ny > kMaxDim || nz > kMaxDim)
@@ -281,9 +279,9 @@ static int plan(int nx, int ny, int nz, Plan &pl) {
     pl.nb = (pl.d.n + kBrick - 1) / kBrick;
     pl.empty = nx < 2 || ny < 2 || nz < 2;
     pl.off_cnt = 256;
-    pl.off_offs = pl.off_cnt + up256(sizeof(uint32_t) * (size_t)pl.nb);
-    pl.off_map = pl.off_offs + up256(2 * sizeof(int64_t) * (size_t)pl.nb);
-    pl.total = pl.off_map + up256(3 * sizeof(int32_t) * (size_t)pl.d.n);
+    pl.off_offs = pl.off_cnt + align256(sizeof(uint32_t) * (size_t)pl.nb);
+    pl.off_map = pl.off_offs + align256(2 * sizeof(int64_t) * (size_t)pl.nb);
+    pl.total = pl.off_map + align256(3 * sizeof(int32_t) * (size_t)pl.d.n);
     return PNR_OK;
 }
 

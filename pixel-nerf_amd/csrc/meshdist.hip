@@ -164,8 +164,6 @@ struct Plan {
     size_t off_gtot, off_goff, off_cdf, total;   // Header at offset 0
 };
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static int plan(int64_t n_faces, Plan &pl) {
     if (n_faces < 1) return fail(PNR_ERR_INVALID, "mesh sample: n_faces must be >= 1 (got %lld)", (long long)n_faces);
     if (n_faces > kMaxCount)
@@ -173,9 +171,9 @@ static int plan(int64_t n_faces, Plan &pl) {
     pl.nt = (uint32_t)n_faces;
     pl.ng = (pl.nt + (uint32_t)kGroup - 1) / (uint32_t)kGroup;
     pl.off_gtot = 256;
-    pl.off_goff = pl.off_gtot + up256(sizeof(double) * (size_t)pl.ng);
-    pl.off_cdf = pl.off_goff + up256(sizeof(double) * (size_t)pl.ng);
-    pl.total = pl.off_cdf + up256(sizeof(double) * (size_t)pl.nt);
+    pl.off_goff = pl.off_gtot + align256(sizeof(double) * (size_t)pl.ng);
+    pl.off_cdf = pl.off_goff + align256(sizeof(double) * (size_t)pl.ng);
+    pl.total = pl.off_cdf + align256(sizeof(double) * (size_t)pl.nt);
     return PNR_OK;
 }
 
@@ -294,7 +292,7 @@ static int plan(int64_t n, int64_t m, Plan &pl) {
     pl.m = (uint32_t)m;
     pl.slices = (uint32_t)((m + kSlice - 1) / kSlice);
     // one slice writes the outputs directly; 256 bytes keep "0 = refused" unambiguous
-    const size_t part = pl.slices > 1 ? msk::up256(sizeof(float) * (size_t)pl.slices * (size_t)n) : 0;
+    const size_t part = pl.slices > 1 ? align256(sizeof(float) * (size_t)pl.slices * (size_t)n) : 0;
     pl.off_idx = part;
     pl.total = pl.slices > 1 ? 2 * part : 256;
     return PNR_OK;

@@ -179,7 +179,7 @@ static int plan(int64_t n, int h, int w, int c, Shape &sh, size_t &bytes) {
     if (n > kMaxBlocks / per_image)
         return fail(PNR_ERR_UNSUPPORTED, "image metrics: %lld images of %d x %d x %d need more than %lld workgroups",
                     (long long)n, h, w, c, (long long)kMaxBlocks);
-    bytes = ((size_t)(n * per_image) * 2 * sizeof(double) + 255) & ~(size_t)255;
+    bytes = align256((size_t)(n * per_image) * 2 * sizeof(double));
     return PNR_OK;
 }
 

@@ -894,12 +894,33 @@ static std::atomic<int> g_mlp_last_kernel{PNR_MLP_KERNEL_NONE};
 int mlp_set_lean(int on) { return g_mlp_lean.exchange(on != 0); }
 int mlp_last_kernel() { return g_mlp_last_kernel.load(std::memory_order_relaxed); }
 
-// Launch the fused model over n_points points (render mode if rays != nullptr).
-int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *packed,
-                     const float *rays, const float *zs, int K, int64_t rays_per_obj,
-                     const float *xyz, const float *dirs, int64_t points_per_obj,
-                     int64_t n_points, float *out, float *xsum_ws, hipStream_t st, float *save,
-                     const float *proj, const MarchCfg *march) {
+// Kernel selection.  PREC comes from the descriptor's precision, PZ / MARCH / LEAN from the call;
+// exactly the instantiations that exist: PZ x MARCH for every PREC (f16, PREC 1, has no
+// latent-gather form: launch_point_mlp refuses it), and LEAN for the two fp16 modes.
+template <int PREC, bool PZ, bool MARCH, bool LEAN = false>
+static void launch_kernel(unsigned grid, size_t lds, hipStream_t st, const mlpk::Args &a) {
+    hipLaunchKernelGGL((mlpk::k_point_mlp<PREC, PZ, MARCH, LEAN>), dim3(grid), dim3(mlpk::NTHR), lds, st, a);
+}
+template <int PREC>
+static void select_kernel(bool pz, bool march, bool lean, unsigned grid, size_t lds, hipStream_t st,
+                          const mlpk::Args &a) {
+    if constexpr (mlpk::is_h(PREC)) {
+        if (lean) return launch_kernel<PREC, true, true, true>(grid, lds, st, a);
+    }
+    if constexpr (PREC != 1) {
+        if (!pz) return march ? launch_kernel<PREC, false, true>(grid, lds, st, a)
+                              : launch_kernel<PREC, false, false>(grid, lds, st, a);
+    }
+    return march ? launch_kernel<PREC, true, true>(grid, lds, st, a)
+                 : launch_kernel<PREC, true, false>(grid, lds, st, a);
+}
+
+// Launch the fused model over c.n_points points (render mode if c.rays != nullptr).
+int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const PointMlpCall &c, hipStream_t st) {
+    const float *const proj = c.proj, *const rays = c.rays, *const save = c.save;
+    const MarchCfg *const march = c.march;
+    const int K = c.K;
+    const int64_t n_points = c.n_points;
     if (n_points == 0) return PNR_OK;
     if (d.precision == PNR_PREC_F16 && (!proj || save))
         return fail(PNR_ERR_UNSUPPORTED, "precision 1 (f16) is inference only on the projected-latent path: it "
@@ -915,61 +936,44 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const void *pac
         return fail(PNR_ERR_INVALID, "point_mlp: the single-launch march needs kc = 64, kc + kf = 64 kpt_f, both "
                     "packs and projections, fine outputs, and n_points = n_rays (kc + kc + kf)");
     mlpk::Args a = {};
-    a.packed = static_cast<const float *>(packed);
+    a.packed = static_cast<const float *>(c.packed);
     a.L = mlpk::make_layout(d);
     a.render_mode = rays != nullptr;
-    a.rays = rays; a.zs = zs; a.K = K; a.rays_per_obj = rays_per_obj;
-    a.xyz = xyz; a.dirs = dirs; a.points_per_obj = points_per_obj;
+    a.rays = rays; a.zs = c.z; a.K = K; a.rays_per_obj = c.rays_per_obj;
+    a.xyz = c.xyz; a.dirs = c.dirs; a.points_per_obj = c.points_per_obj;
     a.n_points = n_points;
     a.latent = sc.latent; a.cams = sc.cams;
     a.ns = sc.n_views; a.hl = sc.latent_h; a.wl = sc.latent_w;
     a.img_w = sc.image_w; a.img_h = sc.image_h;
-    a.out = out;
-    a.xsum = xsum_ws;
+    a.out = c.out;
+    a.xsum = c.xsum;
     a.march = march != nullptr;
     if (march) a.m = *march;
     a.n_tiles = (n_points + mlpk::COLS - 1) / mlpk::COLS;
-    a.save = save;
+    a.save = c.save;
     a.proj = proj;
     a.proj_stride = (int64_t)sc.n_obj * sc.n_views * sc.latent_h * sc.latent_w * mlpk::H;
     const int cus = device_cu_count();
     if (a.n_tiles >= (1ll << 31)) return fail(PNR_ERR_UNSUPPORTED, "more than 2^31 point tiles in one launch");
-    a.tile_ctr = reinterpret_cast<int *>(xsum_ws + (size_t)cus * 2 * mlpk::COLS * mlpk::H);
+    a.tile_ctr = reinterpret_cast<int *>(c.xsum + (size_t)cus * 2 * mlpk::COLS * mlpk::H);
     if (hipMemsetAsync(a.tile_ctr, 0, 512, st) != hipSuccess) return fail(PNR_ERR_HIP, "point_mlp: hipMemsetAsync failed");
-    const int64_t grid = a.n_tiles < cus ? a.n_tiles : cus;
-    size_t lds = mlpk::lds_bytes(mlpk::fwd_lds(mlpk::is_h(d.precision)), march != nullptr);
+    const unsigned grid = (unsigned)(a.n_tiles < cus ? a.n_tiles : cus);
     // The lean instantiation: a render (rays) of ONE source view on the projected latent by a
     // per-pass fused march (modes 1 and 2, not the single launch), no activation save, f16x3 or
-    // f16.  Every other descriptor takes the general instantiations below.
+    // f16.  Every other descriptor takes the general instantiations.
     const bool lean = g_mlp_lean.load(std::memory_order_relaxed) && mlpk::is_h(d.precision) && proj && march &&
                       !march->single && rays && sc.n_views == 1 && !save;
     g_mlp_last_kernel.store(lean ? PNR_MLP_KERNEL_LEAN : PNR_MLP_KERNEL_GENERAL, std::memory_order_relaxed);
-    if (lean) {
-        lds = mlpk::lds_bytes_lean(mlpk::fwd_lds(true));   // the march map + the lean table
-        if (d.precision == PNR_PREC_F16)
-            hipLaunchKernelGGL((mlpk::k_point_mlp<1, true, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
-        else
-            hipLaunchKernelGGL((mlpk::k_point_mlp<3, true, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
-        return launch_ok("point_mlp") ? PNR_OK : PNR_ERR_HIP;
-    }
-#define PNR_LAUNCH_MLP(P)                                                                              \
-    do {                                                                                               \
-        if (proj && march) hipLaunchKernelGGL((mlpk::k_point_mlp<P, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a); \
-        else if (proj) hipLaunchKernelGGL((mlpk::k_point_mlp<P, true, false>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a); \
-        else if (march) hipLaunchKernelGGL((mlpk::k_point_mlp<P, false, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a); \
-        else hipLaunchKernelGGL((mlpk::k_point_mlp<P, false, false>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);     \
-    } while (0)
+    const bool pz = proj != nullptr, fused = march != nullptr;
+    const size_t lds = lean ? mlpk::lds_bytes_lean(mlpk::fwd_lds(true))   // the march map + the lean table
+                            : mlpk::lds_bytes(mlpk::fwd_lds(mlpk::is_h(d.precision)), fused);
     switch (d.precision) {
-    case PNR_PREC_F16:   // PZ only (checked above)
-        if (march) hipLaunchKernelGGL((mlpk::k_point_mlp<1, true, true>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
-        else hipLaunchKernelGGL((mlpk::k_point_mlp<1, true, false>), dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
-        break;
-    case PNR_PREC_F16X3: PNR_LAUNCH_MLP(3); break;
-    case PNR_PREC_BF16X6: PNR_LAUNCH_MLP(6); break;
-    case PNR_PREC_BF16X9: PNR_LAUNCH_MLP(9); break;
-    default: PNR_LAUNCH_MLP(0);
+    case PNR_PREC_F16: select_kernel<1>(pz, fused, lean, grid, lds, st, a); break;
+    case PNR_PREC_F16X3: select_kernel<3>(pz, fused, lean, grid, lds, st, a); break;
+    case PNR_PREC_BF16X6: select_kernel<6>(pz, fused, lean, grid, lds, st, a); break;
+    case PNR_PREC_BF16X9: select_kernel<9>(pz, fused, lean, grid, lds, st, a); break;
+    default: select_kernel<0>(pz, fused, lean, grid, lds, st, a);
     }
-#undef PNR_LAUNCH_MLP
     return launch_ok("point_mlp") ? PNR_OK : PNR_ERR_HIP;
 }
 

@@ -1,6 +1,7 @@
 // Shared helpers for the pixelNeRF gfx950 kernels (internal header).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/pnr_abi.h"
@@ -12,7 +13,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr int kWave = 64;
 
 // ---- error reporting (thread-local; no exceptions cross the ABI) ------------
-void set_error(const char *fmt, ...);
+// records the text pnr_last_error returns and hands `status` back
 int fail(int status, const char *fmt, ...);
 
 // multiprocessor count of the current device (cached per device id)
@@ -21,11 +22,14 @@ int device_cu_count();
 inline bool launch_ok(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
+        fail(PNR_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
         return false;
     }
     return true;
 }
+
+// workspace regions start on 256-byte boundaries
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---- device helpers ------------------------------------------------------------
 // Round-to-nearest fp32 arithmetic without contraction: the reference evaluates

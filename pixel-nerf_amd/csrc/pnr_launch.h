@@ -1,6 +1,6 @@
 // Host launchers and size helpers behind the C ABI (abi.cpp), each declared once with its default
-// arguments.  Every .hip file that defines one includes this header, so a definition that drifts
-// from its declaration fails to compile.
+// arguments and with the parameter names of its definition.  Every .hip file that defines one
+// includes this header, so a definition whose types drift from its declaration fails to compile.
 #pragma once
 #include "pnr_common.h"
 
@@ -9,77 +9,104 @@ namespace pnr {
 struct MarchCfg;   // march_dev.h
 
 // march.hip
-int launch_sample_coarse(const float *, int64_t, int, const RngSrc &, int, float *, hipStream_t);
-int launch_sample_fine(const float *, int64_t, int, const float *, const float *, const float *,
-                       int, int, float, const RngSrc &, const RngSrc &, const RngSrc &, int, float *,
-                       hipStream_t, int *origin = nullptr, float *z_new = nullptr);
-int launch_rng_fill(const RngSrc &, int64_t, int, float *, hipStream_t);
-int launch_merge_raw(const int *, const float *, const float *, int64_t, int, int, float *, hipStream_t);
-int launch_gen_rays(const float *, int64_t, int, int, int, float, float, float, float, float, float,
-                    float *, hipStream_t);
-int launch_composite(const float *, const float *, const float *, int64_t, int, int, float *,
-                     float *, float *, hipStream_t);
+int launch_sample_coarse(const float *rays, int64_t n_rays, int kc, const RngSrc &u, int lindisp, float *z,
+                         hipStream_t st);
+int launch_sample_fine(const float *rays, int64_t n_rays, int kc, const float *z_coarse, const float *weights,
+                       const float *depth, int kf, int kfd, float depth_std, const RngSrc &u_fine,
+                       const RngSrc &u_jit, const RngSrc &n_depth, int lindisp, float *z_fine, hipStream_t st,
+                       int *origin = nullptr, float *z_new = nullptr);
+int launch_rng_fill(const RngSrc &r, int64_t n_rays, int width, float *out, hipStream_t st);
+int launch_merge_raw(const int *origin, const float *raw_c, const float *raw_new, int64_t n_rays, int kc, int kf,
+                     float *raw_f, hipStream_t st);
+int launch_gen_rays(const float *poses, int64_t n_images, int pose_rows, int width, int height, float fx, float fy,
+                    float cx, float cy, float near, float far, float *rays, hipStream_t st);
+int launch_composite(const float *z, const float *raw, const float *rays, int64_t n_rays, int K, int white_bkgd,
+                     float *weights, float *rgb, float *depth, hipStream_t st);
 int sort_width(int n);
 // mlp_pack.hip
-size_t mlp_packed_bytes(const pnr_mlp_desc &);
-int mlp_check_desc(const pnr_mlp_desc &);
-int mlp_pack(const pnr_mlp_weights &, void *, size_t, hipStream_t);
-size_t mlp_packed_t_bytes(const pnr_mlp_desc &);
-int mlp_pack_t(const pnr_mlp_weights &, const void *, void *, size_t, hipStream_t);
+size_t mlp_packed_bytes(const pnr_mlp_desc &d);
+int mlp_check_desc(const pnr_mlp_desc &d);
+int mlp_pack(const pnr_mlp_weights &w, void *packed, size_t bytes, hipStream_t st);
+size_t mlp_packed_t_bytes(const pnr_mlp_desc &d);
+int mlp_pack_t(const pnr_mlp_weights &w, const void *packed, void *packed_t, size_t bytes, hipStream_t st);
 // mlp.hip
 size_t mlp_xsum_bytes(int ns);
 int64_t mlp_save_floats(const pnr_mlp_desc &d, int64_t n_points);
-int launch_point_mlp(const pnr_scene &, const pnr_mlp_desc &, const void *, const float *,
-                     const float *, int, int64_t, const float *, const float *, int64_t, int64_t,
-                     float *, float *, hipStream_t, float *save = nullptr, const float *proj = nullptr,
-                     const MarchCfg *march = nullptr);
+// One launch of the fused point model: n_points points drawn from EITHER the render source (point
+// p is sample p % K of ray p / K) OR the query source (explicit positions).
+struct PointMlpCall {
+    const void *packed = nullptr;      // packed weights (pnr_mlp_pack)
+    const float *proj = nullptr;       // projected latent (pnr_latent_project), or NULL: the latent gather path
+    // render source
+    const float *rays = nullptr;       // (n_rays, 8); non-NULL selects render mode
+    const float *z = nullptr;          // (n_rays, K) depths (drawn by the kernel itself under `march`)
+    int K = 0;
+    int64_t rays_per_obj = 1;
+    // query source
+    const float *xyz = nullptr;        // (n_points, 3)
+    const float *dirs = nullptr;       // (n_points, 3) or NULL
+    int64_t points_per_obj = 1;
+    int64_t n_points = 0;
+    float *out = nullptr;              // (n_points, 4) raw outputs, or NULL (a fused march composites them)
+    float *save = nullptr;             // activation save of the training forward, or NULL
+    const MarchCfg *march = nullptr;   // fused ray march in the kernel's prologue / epilogue, or NULL
+    float *xsum = nullptr;             // workspace of mlp_xsum_bytes()
+};
+int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const PointMlpCall &c, hipStream_t st);
 int mlp_set_lean(int on);   // the lean instantiation's process-wide switch (returns the previous setting)
 int mlp_last_kernel();      // PNR_MLP_KERNEL_* of the last launch_point_mlp
 // mlp_bwd.hip
-int launch_mlp_bwd(const pnr_mlp_desc &, const void *, const void *, const float *, const float *, const float *,
-                   int64_t, float *, float *, hipStream_t, float *, void *, size_t, int n_views);
-size_t mlp_bwd_workspace_bytes(const pnr_mlp_desc &, int64_t);
+int launch_mlp_bwd(const pnr_mlp_desc &d, const void *packed, const void *packed_t, const float *w_out,
+                   const float *save, const float *d_o, int64_t n_points, float *dy, float *dzlat, hipStream_t st,
+                   float *d_bias, void *ws, size_t ws_bytes, int n_views);
+size_t mlp_bwd_workspace_bytes(const pnr_mlp_desc &d, int64_t n_points);
 // wgrad.hip
-size_t wgrad_workspace_bytes(int, int64_t);
-int launch_wgrad(const float *const *, const float *const *, float *const *, int, int64_t, void *, size_t,
-                 hipStream_t, int arith);
+size_t wgrad_workspace_bytes(int n_jobs, int64_t n_points);
+int launch_wgrad(const float *const *dy, const float *const *x, float *const *g, int n_jobs, int64_t n_points,
+                 void *ws, size_t ws_bytes, hipStream_t st, int arith);
 // encoder.hip
-int launch_fold_bn(const pnr_bn_fold *, int, int64_t, hipStream_t);
-int launch_latent_cl_bwd(const float *, float *const *, const int32_t *, const int32_t *, const int32_t *, int, int, int,
-                         int, hipStream_t);
-int launch_latent_cl(const float *const *, const int32_t *, const int32_t *, const int32_t *, int, int, float *,
-                     int, int, bool, hipStream_t);
+int launch_fold_bn(const pnr_bn_fold *folds, int n_folds, int64_t max_elems, hipStream_t st);
+int launch_latent_cl_bwd(const float *g, float *const *d_maps, const int32_t *channels, const int32_t *heights,
+                         const int32_t *widths, int n_maps, int n_images, int out_h, int out_w, hipStream_t st);
+int launch_latent_cl(const float *const *maps, const int32_t *channels, const int32_t *heights,
+                     const int32_t *widths, int n_maps, int n_images, float *latent_cl, int out_h, int out_w,
+                     bool nhwc, hipStream_t st);
 // train.hip
-int launch_composite_bwd(const float *, const float *, const float *, int64_t, int, int, const float *,
-                         const float *, const float *, float *, float *, hipStream_t);
-int launch_points_in_bwd(const float *, const float *, int, int64_t, int64_t, int, const float *, const float *,
-                         int, int, float, float, const float *, int, const float *, const float *, float *,
-                         float *, const uint8_t *, hipStream_t);
+int launch_composite_bwd(const float *z, const float *raw, const float *rays, int64_t n_rays, int K,
+                         int white_bkgd, const float *d_rgb, const float *d_depth, const float *d_weights,
+                         float *d_raw, float *d_z, hipStream_t st);
+int launch_points_in_bwd(const pnr_scene &sc, const pnr_rays &rays, const float *zs, int K, const float *pe,
+                         int pe_n, const float *d_feat, const float *d_zlat, float *d_latent, float *d_z,
+                         const uint8_t *z_mask, hipStream_t st);
 // proj.hip
-int64_t latent_proj_floats(const pnr_scene &, const pnr_mlp_desc &);
-int launch_latent_proj(const pnr_scene &, const pnr_mlp_weights &, float *, size_t, hipStream_t);
+int64_t latent_proj_floats(const pnr_scene &sc, const pnr_mlp_desc &d);
+int launch_latent_proj(const pnr_scene &sc, const pnr_mlp_weights &w, float *proj, size_t bytes, hipStream_t st);
 // mcubes.hip
-size_t mc_workspace_bytes(int, int, int);
+size_t mc_workspace_bytes(int nx, int ny, int nz);
 void mc_case_table(int8_t out[256][16]);
-int launch_mc_count(const float *, int, int, int, float, void *, size_t, int64_t *, hipStream_t);
-int launch_mc_emit(const float *, int, int, int, float, void *, size_t, float *, int64_t, int32_t *, int64_t,
-                   hipStream_t);
+int launch_mc_count(const float *grid, int nx, int ny, int nz, float level, void *ws, size_t bytes,
+                    int64_t *counts_dev, hipStream_t st);
+int launch_mc_emit(const float *grid, int nx, int ny, int nz, float level, void *ws, size_t bytes, float *verts,
+                   int64_t verts_cap, int32_t *faces, int64_t faces_cap, hipStream_t st);
 // metrics.hip
-size_t image_metrics_workspace_bytes(int64_t, int, int, int);
-int launch_image_metrics(const float *, const float *, int64_t, int, int, int, float, float, float, void *, size_t,
-                         double *, hipStream_t);
+size_t image_metrics_workspace_bytes(int64_t n, int h, int w, int c);
+int launch_image_metrics(const float *x, const float *y, int64_t n, int h, int w, int c, float data_range, float k1,
+                         float k2, void *ws, size_t ws_bytes, double *out, hipStream_t st);
 // meshdist.hip
-size_t mesh_sample_workspace_bytes(int64_t);
-int launch_mesh_sample(const float *, int64_t, const int32_t *, int64_t, int64_t, uint64_t, void *, size_t, float *,
-                       float *, int32_t *, double *, hipStream_t);
-size_t nearest_workspace_bytes(int64_t, int64_t);
-int launch_nearest(const float *, int64_t, const float *, int64_t, void *, size_t, float *, int32_t *, hipStream_t);
-int launch_mesh_distance_reduce(const float *, const int32_t *, int64_t, const float *, const int32_t *, int64_t,
-                                const float *, const float *, double, double *, hipStream_t);
+size_t mesh_sample_workspace_bytes(int64_t n_faces);
+int launch_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, int64_t n,
+                       uint64_t seed, void *ws, size_t bytes, float *points, float *normals, int32_t *tri,
+                       double *total_area, hipStream_t st);
+size_t nearest_workspace_bytes(int64_t n, int64_t m);
+int launch_nearest(const float *a, int64_t n, const float *b, int64_t m, void *ws, size_t bytes, float *d2,
+                   int32_t *idx, hipStream_t st);
+int launch_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64_t n, const float *d2_ba,
+                                const int32_t *idx_ba, int64_t m, const float *normals_a, const float *normals_b,
+                                double tau, double *out, hipStream_t st);
 // winding.hip
-size_t winding_workspace_bytes(int64_t, int64_t);
-int launch_winding(const float *, int64_t, const int32_t *, int64_t, const float *, int64_t, void *, size_t, double *,
-                   hipStream_t);
-int launch_box_sample(const float[3], const float[3], int64_t, uint64_t, float *, hipStream_t);   // lo, extent
+size_t winding_workspace_bytes(int64_t n, int64_t n_faces);
+int launch_winding(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *points,
+                   int64_t n, void *ws, size_t bytes, double *w, hipStream_t st);
+int launch_box_sample(const float lo[3], const float ext[3], int64_t n, uint64_t seed, float *points, hipStream_t st);
 
 }  // namespace pnr

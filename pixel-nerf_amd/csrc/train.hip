@@ -333,15 +333,15 @@ int launch_composite_bwd(const float *z, const float *raw, const float *rays, in
     return launch_ok("composite_bwd") ? PNR_OK : PNR_ERR_HIP;
 }
 
-int launch_points_in_bwd(const float *rays, const float *zs, int K, int64_t rays_per_obj, int64_t n_points,
-                         int ns, const float *cams, const float *latent, int hl, int wl, float img_w, float img_h,
-                         const float *pe, int pe_n, const float *d_feat, const float *d_zlat,
-                         float *d_latent, float *d_z, const uint8_t *z_mask, hipStream_t st) {
+int launch_points_in_bwd(const pnr_scene &sc, const pnr_rays &rays, const float *zs, int K, const float *pe,
+                         int pe_n, const float *d_feat, const float *d_zlat, float *d_latent, float *d_z,
+                         const uint8_t *z_mask, hipStream_t st) {
+    const int64_t n_points = rays.n_rays * K;
     if (n_points == 0) return PNR_OK;
     const int64_t waves = (n_points + RUN - 1) / RUN;
-    hipLaunchKernelGGL(k_points_in_bwd, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rays, zs, K,
-                       rays_per_obj, n_points, ns, cams, latent, hl, wl, img_w, img_h, pe, pe_n, d_feat, d_zlat,
-                       d_latent, d_z, z_mask);
+    hipLaunchKernelGGL(k_points_in_bwd, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rays.rays, zs, K,
+                       rays.rays_per_obj, n_points, sc.n_views, sc.cams, sc.latent, sc.latent_h, sc.latent_w,
+                       sc.image_w, sc.image_h, pe, pe_n, d_feat, d_zlat, d_latent, d_z, z_mask);
     return launch_ok("points_in_bwd") ? PNR_OK : PNR_ERR_HIP;
 }
 

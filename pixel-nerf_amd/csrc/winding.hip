@@ -178,7 +178,7 @@ static int plan(int64_t n, int64_t n_faces, Plan &pl) {
     pl.nt = (uint32_t)n_faces;
     pl.slices = (uint32_t)((n_faces + kSlice - 1) / kSlice);
     // one slice writes w directly; 256 bytes keep "0 = refused" unambiguous
-    pl.total = pl.slices > 1 ? ((sizeof(double) * (size_t)pl.slices * (size_t)n + 255) & ~(size_t)255) : 256;
+    pl.total = pl.slices > 1 ? align256(sizeof(double) * (size_t)pl.slices * (size_t)n) : 256;
     return PNR_OK;
 }
 
