@@ -18,14 +18,16 @@
  *     arguments themselves (host memory, read during the call only).
  *   - All tensors are fp32, C-contiguous, row-major, in the shapes given below (exceptions:
  *     the float64 `out` of pnr_image_metrics and pnr_mesh_distance_reduce, the float64
- *     `total_area` of pnr_mesh_sample, the float64 `w` of pnr_winding, and the int32 index
- *     tensors named as such).  The `lo` / `hi` of pnr_box_sample are host arrays.
+ *     `total_area` of pnr_mesh_sample, the float64 `w` of pnr_winding, the float64 `out` and int64
+ *     `order` / `seg_start` of pnr_mesh_component_sums, and the int32 index tensors named as such).
+ *     The `lo` / `hi` of pnr_box_sample and the `launches` of pnr_mesh_components are host memory.
  *   - Calls are asynchronous and stream-ordered on `stream` (a hipStream_t; NULL
  *     = the default stream).  The library never allocates device memory: scratch
  *     comes from a caller-provided workspace sized by the *_workspace_bytes query.
- *     Two calls wait for their stream before they return: pnr_mc_emit, which reads the two
- *     counted totals back to check the caller's capacities, and pnr_mesh_sample, which reads its
- *     face-index flag and the total area back before it samples.  pnr_mc_case_table is host-only.
+ *     Three calls wait for their stream before they return: pnr_mc_emit, which reads the two
+ *     counted totals back to check the caller's capacities, pnr_mesh_sample, which reads its
+ *     face-index flag and the total area back before it samples, and pnr_mesh_components, which
+ *     reads its face-index flag back.  pnr_mc_case_table is host-only.
  *   - Functions return PNR_OK (0) or a negative pnr_status; pnr_last_error()
  *     returns a thread-local message for the last failing call on that thread.
  *     No C++ exception crosses this boundary.
@@ -769,6 +771,71 @@ int pnr_winding(const float *verts, int64_t n_verts, const int32_t *faces, int64
 
 /* n in 1 .. 2^31 - 1; lo, hi finite with lo_k <= hi_k (else PNR_ERR_INVALID). */
 int pnr_box_sample(const float *lo, const float *hi, int64_t n, uint64_t seed, float *points, pnr_stream_t stream);
+
+/* ---- Mesh cleanup (weld, connected components, per-component sums; additive in ABI 8) ----------
+ * The reference has no counterpart; the usual host route is trimesh's split.  A density mesh carries
+ * floaters, and one stray blob rescales a mesh that is normalised by its bounds before it is scored:
+ * these three steps find the components of the mesh pnr_mc_emit leaves on the device (or of an STL
+ * soup, once welded) so that the caller can keep the large ones.  All indices are int32.
+ *
+ * Weld (pnr_mesh_weld): verts (n_verts, 3) fp32 -> remap (n_verts) int32.
+ *   Equality  two vertices are equal when their three coordinates compare equal as floats: -0.0
+ *             equals +0.0, and a vertex with a NaN coordinate equals nothing, itself included.
+ *   Result    remap[i] = the LOWEST j whose vertex equals vertex i; remap[i] = i for a NaN vertex.
+ *             remap[remap[i]] == remap[i].  A function of verts alone: each class settles at its
+ *             minimum whatever the order its members arrive in (integer atomicCAS / atomicMin on a
+ *             hash table in the workspace; csrc/meshclean.hip).
+ *   Limits    n_verts in 1 .. 2^29 (larger: PNR_ERR_UNSUPPORTED).  No host sync.
+ *
+ * Components (pnr_mesh_components): faces (n_faces, 3) int32 over n_verts vertices -> vert_label
+ * (n_verts) int32, face_label (n_faces) int32.
+ *   Connected two vertices are connected when a face names both; components are the classes of the
+ *             transitive closure.  A vertex that no face names is a component of its own.
+ *   Labels    vert_label[v] = the lowest vertex index of v's component; face_label[t] = the label of
+ *             face t's vertices.  n_faces = 0 is allowed (faces and face_label may then be NULL).
+ *   Indices   a face with an index outside [0, n_verts) is never read through; it sets a flag, its
+ *             face_label is -1 and the call returns PNR_ERR_INVALID.
+ *   Schedule  lock-free union-find with min-hooking in ONE pass over the faces, then one flatten
+ *             pass: *launches (HOST memory, may be NULL) receives the number of kernel launches the
+ *             call took (3; 2 without faces).  No fixed-point iteration, so no round ceiling.  The
+ *             call waits for its stream once to read the index flag, as pnr_mesh_sample does.
+ *   Limits    n_verts in 1 .. 2^31 - 1, n_faces in 0 .. 2^31 - 1.
+ *
+ * Sums (pnr_mesh_component_sums): per component its area and signed volume, out (n_components, 2)
+ * FLOAT64 = {area, signed volume}.
+ *   Input     order (n_faces) int64: the face indices grouped by component, ascending within a
+ *             component (a stable sort of the faces by component id); seg_start (n_components + 1)
+ *             int64: component c owns order[seg_start[c] .. seg_start[c + 1]).
+ *   Terms     per face (a, b, c), in fp64 from the fp32 vertices, every operation rounded once:
+ *             area = 0.5 * sqrt((nx nx + ny ny) + nz nz), n = (b - a) x (c - a) with
+ *             n.x = u.y w.z - u.z w.y, ...; volume term = (a.x m.x + a.y m.y) + a.z m.z, m = b x c.
+ *             A face (or an entry of order) with an index out of range contributes 0.
+ *   Order     with B = 1024: position k of the component's run is added by thread k mod B, each
+ *             thread in ascending k from 0; the 64 threads of a wave are folded by a butterfly
+ *             (xor 32, 16, .. 1) and the 16 waves added in ascending order from wave 0's; the volume
+ *             sum is divided once by 6.  A function of the component's own face sequence: bit-identical
+ *             from run to run and whether the mesh is processed alone or inside a larger one.
+ *   No atomics, no workspace, no host sync. */
+#define PNR_MESH_CLEAN_BLOCK 256 /* threads (vertices or faces) per workgroup of the weld / component kernels */
+
+/* Workspace bytes of pnr_mesh_weld (the table: 4 bytes x the power of two >= 2 n_verts, at least
+ * 256 slots); 0 if n_verts is outside 1 .. 2^29. */
+size_t pnr_mesh_weld_workspace_bytes(int64_t n_verts);
+
+int pnr_mesh_weld(const float *verts, int64_t n_verts, void *workspace, size_t workspace_bytes, int32_t *remap,
+                  pnr_stream_t stream);
+
+/* Workspace bytes of pnr_mesh_components (the flag and one parent per vertex); 0 for sizes it refuses. */
+size_t pnr_mesh_components_workspace_bytes(int64_t n_verts, int64_t n_faces);
+
+int pnr_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_verts, void *workspace,
+                        size_t workspace_bytes, int32_t *vert_label, int32_t *face_label, int32_t *launches,
+                        pnr_stream_t stream);
+
+/* n_verts, n_faces, n_components in 1 .. 2^31 - 1; out 8-byte aligned. */
+int pnr_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                            const int64_t *order, const int64_t *seg_start, int64_t n_components, double *out,
+                            pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

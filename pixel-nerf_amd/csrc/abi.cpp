@@ -1,8 +1,9 @@
 // extern "C" entry points of libpnr.so (declared in include/pnr_abi.h):
 // argument validation, workspace carving and the stream-ordered launch
-// sequence of the coarse + fine ray march.  No allocation, no host sync (two calls wait for
+// sequence of the coarse + fine ray march.  No allocation, no host sync (three calls wait for
 // their stream: pnr_mc_emit, where mcubes.hip reads the counted totals back to check the
-// capacities, and pnr_mesh_sample, where meshdist.hip reads its index flag and the total area).
+// capacities, pnr_mesh_sample, where meshdist.hip reads its index flag and the total area, and
+// pnr_mesh_components, where meshclean.hip reads its index flag).
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -785,6 +786,49 @@ int pnr_box_sample(const float *lo, const float *hi, int64_t n, uint64_t seed, f
         if (!std::isfinite(ext[k])) return fail(PNR_ERR_INVALID, "pnr_box_sample: the extent of axis %d overflows", k);
     }
     return launch_box_sample(lo, ext, n, seed, points, (hipStream_t)stream);
+}
+
+size_t pnr_mesh_weld_workspace_bytes(int64_t n_verts) { return mesh_weld_workspace_bytes(n_verts); }
+
+int pnr_mesh_weld(const float *verts, int64_t n_verts, void *workspace, size_t workspace_bytes, int32_t *remap,
+                  pnr_stream_t stream) {
+    if (n_verts < 1) return fail(PNR_ERR_INVALID, "pnr_mesh_weld: n_verts must be >= 1");
+    if (!verts || !remap || !workspace) return fail(PNR_ERR_INVALID, "pnr_mesh_weld: NULL argument");
+    if (misaligned(3, verts, remap, workspace))
+        return fail(PNR_ERR_INVALID, "pnr_mesh_weld: verts, remap and workspace must be 4-byte aligned");
+    return launch_mesh_weld(verts, n_verts, workspace, workspace_bytes, remap, (hipStream_t)stream);
+}
+
+size_t pnr_mesh_components_workspace_bytes(int64_t n_verts, int64_t n_faces) {
+    return mesh_components_workspace_bytes(n_verts, n_faces);
+}
+
+int pnr_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_verts, void *workspace,
+                        size_t workspace_bytes, int32_t *vert_label, int32_t *face_label, int32_t *launches,
+                        pnr_stream_t stream) {
+    if (n_verts < 1 || n_faces < 0)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_components: n_verts must be >= 1 and n_faces >= 0");
+    if (!vert_label || !workspace || (n_faces > 0 && (!faces || !face_label)))
+        return fail(PNR_ERR_INVALID, "pnr_mesh_components: NULL argument");
+    if (misaligned(3, faces, vert_label, face_label, workspace))
+        return fail(PNR_ERR_INVALID,
+                    "pnr_mesh_components: faces, vert_label, face_label and workspace must be 4-byte aligned");
+    return launch_mesh_components(faces, n_faces, n_verts, workspace, workspace_bytes, vert_label, face_label, launches,
+                                  (hipStream_t)stream);
+}
+
+int pnr_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                            const int64_t *order, const int64_t *seg_start, int64_t n_components, double *out,
+                            pnr_stream_t stream) {
+    if (n_verts < 1 || n_faces < 1 || n_components < 1)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_component_sums: n_verts, n_faces and n_components must be >= 1");
+    if (!verts || !faces || !order || !seg_start || !out)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_component_sums: NULL argument");
+    if (misaligned(3, verts, faces) || misaligned(7, order, seg_start, out))
+        return fail(PNR_ERR_INVALID,
+                    "pnr_mesh_component_sums: verts and faces must be 4-byte, order, seg_start and out 8-byte aligned");
+    return launch_mesh_component_sums(verts, n_verts, faces, n_faces, order, seg_start, n_components, out,
+                                      (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -108,5 +108,14 @@ size_t winding_workspace_bytes(int64_t n, int64_t n_faces);
 int launch_winding(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *points,
                    int64_t n, void *ws, size_t bytes, double *w, hipStream_t st);
 int launch_box_sample(const float lo[3], const float ext[3], int64_t n, uint64_t seed, float *points, hipStream_t st);
+// meshclean.hip
+size_t mesh_weld_workspace_bytes(int64_t n_verts);
+int launch_mesh_weld(const float *verts, int64_t n_verts, void *ws, size_t bytes, int32_t *remap, hipStream_t st);
+size_t mesh_components_workspace_bytes(int64_t n_verts, int64_t n_faces);
+int launch_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_verts, void *ws, size_t bytes,
+                           int32_t *vert_label, int32_t *face_label, int32_t *launches, hipStream_t st);
+int launch_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                               const int64_t *order, const int64_t *seg_start, int64_t n_components, double *out,
+                               hipStream_t st);
 
 }  // namespace pnr

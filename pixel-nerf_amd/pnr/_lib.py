@@ -158,6 +158,13 @@ SIGNATURES = {
     "pnr_winding_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pnr_winding": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_size, c_vp, c_vp]),
     "pnr_box_sample": (c_i32, [c_vp, c_vp, c_i64, ctypes.c_uint64, c_vp, c_vp]),
+    # mesh cleanup (csrc/meshclean.hip); labels / remap int32, order / seg_start int64, out float64,
+    # launches a host int32
+    "pnr_mesh_weld_workspace_bytes": (c_size, [c_i64]),
+    "pnr_mesh_weld": (c_i32, [c_vp, c_i64, c_vp, c_size, c_vp, c_vp]),
+    "pnr_mesh_components_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pnr_mesh_components": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_size, c_vp, c_vp, ctypes.POINTER(c_i32), c_vp]),
+    "pnr_mesh_component_sums": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
 }
 
 # pnr_weight_grad_arith arithmetics (PNR_WGRAD_*, ABI 4)

@@ -19,7 +19,8 @@ from . import util
 
 __all__ = ["ssim", "psnr_np", "image_metrics", "select_views", "eval_approx", "mesh_metrics", "sample_mesh_np",
            "nearest_np", "MESH_METRIC_NAMES", "volume_iou", "winding_np", "box_sample_np",
-           "VOLUME_METRIC_NAMES"]
+           "VOLUME_METRIC_NAMES", "clean_mesh", "weld_np", "components_np", "component_stats_np",
+           "CLEAN_INFO_NAMES"]
 
 
 def psnr_np(pred, target, data_range=1.0):
@@ -431,3 +432,194 @@ def volume_iou(pred, gt, n_points=100000, seed=0, padding=0.05, backend="auto"):
     box = float(np.prod(hi.astype(np.float64) - lo.astype(np.float64)))
     return {"iou": inter / union if union else 0.0, "volume_pred": n_p / n_points * box,
             "volume_gt": n_g / n_points * box, "n_points": float(n_points)}
+
+
+# ---- mesh cleanup: weld, connected components, floater removal -------------------------------------
+CLEAN_INFO_NAMES = ("n_components", "n_components_kept", "faces_kept")
+
+
+def weld_np(verts):
+    """pnr_mesh_weld's rule on the host (include/pnr_abi.h, "Mesh cleanup"): ``remap (V,) int32``,
+    remap[i] = the lowest index whose three coordinates compare equal to vertex i's as floats (-0.0
+    equals +0.0); a vertex with a NaN coordinate keeps remap[i] = i.  A lexicographic sort, then the
+    minimum index of every run of equal rows."""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    remap = np.arange(v.shape[0], dtype=np.int64)
+    ok = np.nonzero(~np.isnan(v).any(1))[0]
+    if ok.size:
+        w = v[ok] + np.float32(0.0)   # -0 + 0 = +0: equal floats sort next to each other either way
+        order = np.lexsort((w[:, 2], w[:, 1], w[:, 0]))
+        s = w[order]
+        start = np.concatenate([[True], (s[1:] != s[:-1]).any(1)])
+        first = np.minimum.reduceat(ok[order], np.nonzero(start)[0])
+        remap[ok[order]] = first[np.cumsum(start) - 1]
+    return remap.astype(np.int32)
+
+
+def _weld_apply_np(verts, faces):
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("weld: a face index lies outside [0, %d)" % v.shape[0])
+    remap = weld_np(v)
+    keep = remap == np.arange(v.shape[0])
+    new_index = np.cumsum(keep) - 1
+    return v[keep], new_index[remap[f]].astype(np.int32).reshape(-1, 3), remap
+
+
+def components_np(n_verts, faces):
+    """pnr_mesh_components' labels on the host, pure numpy: ``(vert_label (V,) int32, face_label (T,)
+    int32, n_components)``.  Two vertices are connected when a face names both; a label is the lowest
+    vertex index of the component; a vertex no face names is its own component.  Rounds of "every
+    face lowers the labels of its vertices, and of their labels, to the face's minimum", each followed
+    by pointer jumping to a fixed point, until nothing changes."""
+    n_verts = int(n_verts)
+    f = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= n_verts):
+        raise ValueError("components: a face index lies outside [0, %d)" % n_verts)
+    label = np.arange(n_verts, dtype=np.int64)
+    while f.size:
+        cur = label[f]
+        low = cur.min(1)
+        new = label.copy()
+        for k in range(3):
+            np.minimum.at(new, cur[:, k], low)
+            np.minimum.at(new, f[:, k], low)
+        while True:
+            jump = new[new]
+            if np.array_equal(jump, new):
+                break
+            new = jump
+        if np.array_equal(new, label):
+            break
+        label = new
+    face_label = label[f[:, 0]] if f.size else np.zeros(0, np.int64)
+    return label.astype(np.int32), face_label.astype(np.int32), int((label == np.arange(n_verts)).sum())
+
+
+def _face_terms_np(verts, faces):
+    """(area (T,), volume term (T,)) in fp64 from the fp32 vertices, in the header's operation order."""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3).astype(np.float64)
+    f = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    u, w = b - a, c - a
+    nx, ny, nz = (u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2],
+                  u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0])
+    area = 0.5 * np.sqrt((nx * nx + ny * ny) + nz * nz)
+    mx, my, mz = (b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1], b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2],
+                  b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0])
+    return area, (a[:, 0] * mx + a[:, 1] * my) + a[:, 2] * mz
+
+
+def component_stats_np(verts, faces, vert_label, face_label):
+    """ops.mesh_component_stats on the host: the same dict (numpy arrays).  The integer entries are
+    those of the device; area and signed_volume are numpy's fp64 sums of the same per-face terms over
+    each component's faces in ascending order (another summation order than the device's)."""
+    vert_label, face_label = np.asarray(vert_label, np.int32), np.asarray(face_label, np.int32)
+    labels = np.unique(vert_label)
+    n_c = len(labels)
+    vert_id, face_id = np.searchsorted(labels, vert_label), np.searchsorted(labels, face_label)
+    cnt_v = np.bincount(vert_id, minlength=n_c).astype(np.int64)
+    cnt_f = np.bincount(face_id, minlength=n_c).astype(np.int64)
+    area, vol = np.zeros(n_c), np.zeros(n_c)
+    if len(face_id):
+        terms_a, terms_v = _face_terms_np(verts, faces)
+        order = np.argsort(face_id, kind="stable")
+        has = np.nonzero(cnt_f)[0]
+        start = (np.cumsum(cnt_f) - cnt_f)[has]
+        area[has] = np.add.reduceat(terms_a[order], start)
+        vol[has] = np.add.reduceat(terms_v[order], start) / 6.0
+    return {"labels": labels, "vert_id": vert_id.astype(np.int64), "face_id": face_id.astype(np.int64),
+            "n_verts": cnt_v, "n_faces": cnt_f, "area": area, "signed_volume": vol}
+
+
+def _select_components(n_faces, measure, keep, min_frac):
+    """bool (C,): the components that stay.  Only components with faces take part; ``largest`` is the
+    first maximum of the measure (the lowest label on a tie), ``min_frac`` keeps measure >= min_frac *
+    the largest measure (fp64).  A NaN measure counts as 0.  Both backends run this on the host."""
+    has = np.asarray(n_faces) > 0
+    if not has.any():
+        return has
+    m = np.where(has, np.nan_to_num(np.asarray(measure, np.float64), nan=0.0), -np.inf)
+    if keep == "largest":
+        sel = np.zeros(len(m), bool)
+        sel[int(np.argmax(m))] = True
+        return sel
+    if min_frac is not None:
+        return has & (m >= float(min_frac) * m.max())
+    return has
+
+
+def clean_mesh(verts, faces, weld=True, keep="largest", min_frac=None, by="faces", backend="auto"):
+    """Drop the floaters of a mesh: ``(verts', faces', info)`` from verts (V, 3), faces (T, 3), tensors
+    or arrays.  With ``weld`` equal vertices are merged first (an STL soup has one component per
+    triangle until then); the connected components are labelled; ``keep="largest"`` keeps the one
+    component with the most faces (``by="faces"``) or the most area (``by="area"``), a tie going to the
+    lowest label; ``keep="all"`` with ``min_frac=F`` (0 < F <= 1) keeps every component whose measure is
+    >= F times the largest's, and without it every component.  Kept vertices and faces keep their
+    relative order, vertices no kept face names are dropped, faces are re-indexed as int32.  ``info``:
+    ``n_components`` (components that hold a face), ``n_components_kept``, ``faces_kept``.  ``"hip"``
+    runs pnr.ops.mesh_weld / mesh_components / mesh_component_stats on the device the mesh is on (a
+    host mesh is moved to the current HIP device) and returns device tensors; it reads the
+    per-component measure back once and selects on the host with the code the ``"numpy"`` backend
+    uses, which restates the definitions in pure numpy and returns arrays: labels, remaps, kept sets
+    and counts are the same on both (``by="area"`` compares fp64 sums whose last bits differ between
+    the two, so only an exact tie or threshold hit can choose differently).  ``"auto"`` is hip where a
+    HIP device is present."""
+    if backend == "auto":
+        backend = "hip" if torch.cuda.is_available() else "numpy"
+    if backend not in ("hip", "numpy"):
+        raise ValueError("clean_mesh backend must be 'auto', 'numpy' or 'hip' (got %r)" % (backend,))
+    if keep not in ("largest", "all"):
+        raise ValueError("clean_mesh: keep must be 'largest' or 'all' (got %r)" % (keep,))
+    if by not in ("faces", "area"):
+        raise ValueError("clean_mesh: by must be 'faces' or 'area' (got %r)" % (by,))
+    if min_frac is not None:
+        if keep == "largest":
+            raise ValueError("clean_mesh: min_frac goes with keep='all' ('largest' keeps one component)")
+        if not 0.0 < float(min_frac) <= 1.0:
+            raise ValueError("clean_mesh: min_frac must be in (0, 1] (got %r)" % (min_frac,))
+    if backend == "numpy":
+        v, f = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (verts, faces))
+        v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(f, np.int32).reshape(-1, 3)
+        if weld:
+            v, f, _ = _weld_apply_np(v, f)
+        vl, fl, _ = components_np(len(v), f)
+        st = component_stats_np(v, f, vl, fl)
+        sel = _select_components(st["n_faces"], st["n_faces"] if by == "faces" else st["area"], keep, min_frac)
+        faces_k = f[sel[st["face_id"]]] if len(f) else f
+        used = np.zeros(len(v), bool)
+        used[faces_k.reshape(-1)] = True
+        out_v, out_f = v[used], (np.cumsum(used) - 1)[faces_k].astype(np.int32).reshape(-1, 3)
+        n_comp = int((st["n_faces"] > 0).sum())
+    else:
+        from . import ops
+
+        dev = next((t.device for t in (verts, faces) if torch.is_tensor(t) and t.device.type == "cuda"),
+                   torch.device("cuda", torch.cuda.current_device()))
+
+        def on_dev(t, dtype):
+            t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+            return t.to(device=dev, dtype=dtype).reshape(-1, 3).contiguous()
+
+        v, f = on_dev(verts, torch.float32), on_dev(faces, torch.int32)
+        if weld:
+            v, f, _ = ops.mesh_weld(v, f)
+        vl, fl, _ = ops.mesh_components(v, f)
+        st = ops.mesh_component_stats(v, f, vl, fl)
+        # the one read-back of the selection: the exact face counts and the measure, (2, C) fp64
+        host = torch.stack([st["n_faces"].double(), st["n_faces"].double() if by == "faces" else st["area"]])
+        host = host.cpu().numpy()
+        sel = _select_components(host[0], host[1], keep, min_frac)
+        n_comp = int((host[0] > 0).sum())
+        if f.shape[0]:
+            faces_k = f[torch.from_numpy(sel).to(dev)[st["face_id"]]]
+        else:
+            faces_k = f
+        used = torch.zeros(v.shape[0], device=dev, dtype=torch.bool)
+        used[faces_k.long().reshape(-1)] = True
+        out_v = v[used]
+        out_f = (torch.cumsum(used, 0, dtype=torch.int64) - 1)[faces_k.long()].to(torch.int32).reshape(-1, 3)
+    return out_v, out_f, {"n_components": n_comp, "n_components_kept": int(sel.sum()),
+                          "faces_kept": int(out_f.shape[0])}

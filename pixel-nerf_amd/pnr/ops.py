@@ -387,3 +387,131 @@ def box_sample(lo, hi, n, seed=0, device="cuda"):
         _lib.check(lib.pnr_box_sample(ctypes.cast(c_lo, ctypes.c_void_p), ctypes.cast(c_hi, ctypes.c_void_p), n,
                                       int(seed), _lib.ptr(points), _lib.stream_of(dev)), "pnr_box_sample")
     return points
+
+
+# workgroup size of the weld / component kernels (PNR_MESH_CLEAN_BLOCK, include/pnr_abi.h): one
+# thread per vertex or face, so sizes around a multiple of it exercise the partial last workgroup
+MESH_CLEAN_BLOCK = 256
+COMPONENT_STAT_KEYS = ("labels", "vert_id", "face_id", "n_verts", "n_faces", "area", "signed_volume")
+
+
+def mesh_weld_remap(verts):
+    """``remap (V,) int32`` of pnr_mesh_weld (include/pnr_abi.h, "Mesh cleanup"; csrc/meshclean.hip):
+    remap[i] is the lowest index whose vertex has the same three coordinates as vertex i (-0.0 equals
+    +0.0; a vertex with a NaN coordinate maps to itself).  No host sync."""
+    verts = _cloud(verts, "verts")
+    n_v = int(verts.shape[0])
+    dev = verts.device
+    if n_v == 0:
+        return torch.empty(0, device=dev, dtype=torch.int32)
+    lib = _lib.load()
+    nbytes = lib.pnr_mesh_weld_workspace_bytes(n_v)
+    if nbytes == 0:
+        raise _lib.PnrError("pnr_mesh_weld_workspace_bytes: %d vertices not supported (1 .. 2^29)" % n_v)
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    remap = torch.empty(n_v, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mesh_weld(_lib.ptr(verts), n_v, _lib.ptr(ws), nbytes, _lib.ptr(remap), _lib.stream_of(dev)),
+                   "pnr_mesh_weld")
+    return remap
+
+
+def mesh_weld(verts, faces):
+    """Merge equal vertices of a device mesh (an STL soup, say): verts (V, 3) float32, faces (T, 3)
+    int32 -> ``(verts' (V', 3), faces' (T, 3) int32, remap (V,) int32)``.  ``remap`` is
+    ``mesh_weld_remap``'s, in ORIGINAL indices; verts' are the vertices with remap[i] == i in ascending
+    original order and faces' the same T rows re-indexed into them: no face is dropped, degenerate
+    ones included, so row t still is record t of the STL.  One host sync (V' sizes the output)."""
+    verts = _cloud(verts, "verts")
+    faces = _cloud(faces, "faces", torch.int32)
+    if faces.device != verts.device:
+        raise ValueError("pnr: faces is on %s, verts on %s" % (faces.device, verts.device))
+    remap = mesh_weld_remap(verts)
+    n_v = int(verts.shape[0])
+    keep = remap == torch.arange(n_v, device=verts.device, dtype=torch.int32)
+    new_index = torch.cumsum(keep, 0, dtype=torch.int64) - 1
+    if faces.numel() and n_v:
+        f = faces.long()
+        if bool(((f < 0) | (f >= n_v)).any()):
+            raise ValueError("pnr: a face index lies outside [0, %d)" % n_v)
+        faces = new_index[remap.long()[f]].to(torch.int32)
+    elif faces.numel():
+        raise ValueError("pnr: faces over an empty vertex set")
+    return verts[keep], faces.contiguous(), remap
+
+
+def mesh_components(verts_or_n, faces, return_launches=False):
+    """Connected components of an indexed device mesh (include/pnr_abi.h, "Mesh cleanup"): faces (T, 3)
+    int32 over V vertices (``verts_or_n``: the (V, 3) vertex tensor, or V itself) ->
+    ``(vert_label (V,) int32, face_label (T,) int32, n_components)``.  Two vertices are connected when
+    a face names both; a label is the lowest vertex index of the component, and a vertex no face names
+    is a component of its own.  A face index outside [0, V) raises.  ``return_launches`` appends the
+    number of kernel launches the library took.  Two host syncs (the library's index flag, and the
+    count)."""
+    faces = _cloud(faces, "faces", torch.int32)
+    n_v = int(verts_or_n.shape[0]) if torch.is_tensor(verts_or_n) else int(verts_or_n)
+    if n_v < 0:
+        raise ValueError("pnr: the number of vertices must be >= 0 (got %d)" % n_v)
+    n_t = int(faces.shape[0])
+    dev = faces.device
+    if n_v == 0:
+        if n_t:
+            raise ValueError("pnr: faces over an empty vertex set")
+        out = (torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.int32), 0)
+        return out + (0,) if return_launches else out
+    import ctypes
+
+    lib = _lib.load()
+    nbytes = lib.pnr_mesh_components_workspace_bytes(n_v, n_t)
+    if nbytes == 0:
+        raise _lib.PnrError("pnr_mesh_components_workspace_bytes: %d vertices / %d faces not supported (below 2^31)"
+                            % (n_v, n_t))
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    vert_label = torch.empty(n_v, device=dev, dtype=torch.int32)
+    face_label = torch.empty(n_t, device=dev, dtype=torch.int32)
+    launches = ctypes.c_int32(0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mesh_components(_lib.ptr(faces) if n_t else None, n_t, n_v, _lib.ptr(ws), nbytes,
+                                           _lib.ptr(vert_label), _lib.ptr(face_label) if n_t else None,
+                                           ctypes.byref(launches), _lib.stream_of(dev)), "pnr_mesh_components")
+    n_c = int((vert_label == torch.arange(n_v, device=dev, dtype=torch.int32)).sum())
+    out = (vert_label, face_label, n_c)
+    return out + (int(launches.value),) if return_launches else out
+
+
+def mesh_component_stats(verts, faces, vert_label, face_label):
+    """Per-component statistics of a labelled device mesh (``mesh_components``' labels) as a dict of
+    device tensors (COMPONENT_STAT_KEYS): ``labels`` (C,) int32 ascending, the dense id c = 0 .. C - 1
+    of a component being its label's rank; ``vert_id`` (V,) / ``face_id`` (T,) int64 dense ids;
+    ``n_verts`` / ``n_faces`` (C,) int64, exact; ``area`` / ``signed_volume`` (C,) float64
+    (pnr_mesh_component_sums: per-face terms in fp64 from the fp32 vertices, summed in a fixed order
+    that depends on the component's own faces only, so a component's sums are bit-identical from run
+    to run and inside any larger mesh).  The faces are grouped by component with a stable sort; the
+    counts are integer bincounts.  One host sync (C)."""
+    verts = _cloud(verts, "verts")
+    faces = _cloud(faces, "faces", torch.int32)
+    dev = verts.device
+    n_v, n_t = int(verts.shape[0]), int(faces.shape[0])
+    for t, name, n in ((vert_label, "vert_label", n_v), (face_label, "face_label", n_t)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != dev:
+            raise ValueError("pnr: %s must be an int32 tensor of shape (%d,) on %s" % (name, n, dev))
+    if faces.device != dev:
+        raise ValueError("pnr: faces is on %s, verts on %s" % (faces.device, dev))
+    labels = torch.unique(vert_label)   # sorted ascending
+    n_c = int(labels.shape[0])
+    vert_id = torch.searchsorted(labels, vert_label)
+    face_id = torch.searchsorted(labels, face_label)
+    cnt_v = torch.bincount(vert_id, minlength=n_c)
+    cnt_f = torch.bincount(face_id, minlength=n_c)
+    sums = torch.zeros(n_c, 2, device=dev, dtype=torch.float64)
+    if n_t and n_c:
+        order = torch.sort(face_id, stable=True).indices.contiguous()
+        seg = torch.zeros(n_c + 1, device=dev, dtype=torch.int64)
+        seg[1:] = torch.cumsum(cnt_f, 0)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            _lib.check(lib.pnr_mesh_component_sums(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(order),
+                                                   _lib.ptr(seg), n_c, _lib.ptr(sums), _lib.stream_of(dev)),
+                       "pnr_mesh_component_sums")
+    return {"labels": labels, "vert_id": vert_id, "face_id": face_id, "n_verts": cnt_v, "n_faces": cnt_f,
+            "area": sums[:, 0].contiguous(), "signed_volume": sums[:, 1].contiguous()}

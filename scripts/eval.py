@@ -27,7 +27,12 @@ Chamfer-L1 / L2, accuracy / completeness, F-score, normal consistency) and write
 script's --normalize / --gt_radius / --n_samples / --tau / --seed.  With --iou (and --n_iou_points)
 the volumetric IoU (pnr.evaluate.volume_iou: winding-number containment, pnr.ops.mesh_contains,
 csrc/winding.hip) is scored from the same device tensors and its lines follow in that file.  An
-object without a ground-truth file is skipped with one line on stderr."""
+object without a ground-truth file is skipped with one line on stderr.  --components largest or
+--min_component_frac F (scripts/eval_mesh.py's flags) drop the floaters of the device mesh before it
+is scored (pnr.evaluate.clean_mesh: pnr.ops.mesh_weld / mesh_components / mesh_component_stats,
+csrc/meshclean.hip) and add the component counts to mesh_metrics.txt; --write_clean_mesh also writes
+the cleaned mesh as <output>/<object>/<object>_mesh_clean.stl beside the untouched
+<object>_mesh.stl."""
 import argparse
 import os
 import sys
@@ -130,6 +135,8 @@ def main(argv=None):
                     help="ground-truth meshes <object>.stl: score each extracted mesh on the device (needs the "
                          "hip mesh backend) into <object>/mesh_metrics.txt")
     eval_mesh.add_mesh_metric_args(ap)
+    ap.add_argument("--write_clean_mesh", action="store_true",
+                    help="with --components largest / --min_component_frac: also write <object>_mesh_clean.stl")
     ap.add_argument("--ray_batch_size", "-R", type=int, default=50000)
     ap.add_argument("--gpu_id", type=int, default=0)
     ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
@@ -139,6 +146,12 @@ def main(argv=None):
     args.resume = True
     if args.gt_mesh_dir is not None and args.mesh_backend == "skimage":
         ap.error("--gt_mesh_dir scores the device mesh: it needs --mesh_backend hip (or auto without skimage)")
+    if eval_mesh.component_args_error(args):
+        ap.error(eval_mesh.component_args_error(args))
+    if args.write_clean_mesh and not eval_mesh.cleaning(args):
+        ap.error("--write_clean_mesh needs --components largest or --min_component_frac")
+    if args.write_clean_mesh and args.mesh_backend == "skimage":
+        ap.error("--write_clean_mesh cleans the device mesh: it needs --mesh_backend hip (or auto without skimage)")
 
     device = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(device)
@@ -188,6 +201,16 @@ def main(argv=None):
                 name, args.mesh_res, dt, args.mesh_res ** 3 / dt / 1e6, backend, n_tri, dt_mesh,
                 "" if n_tri else ": threshold %g is outside the grid's range, empty STL written" % args.mesh_thresh),
                 flush=True)
+            clean_info = None
+            wanted = args.gt_mesh_dir is not None or args.write_clean_mesh
+            if backend == "hip" and eval_mesh.cleaning(args) and wanted:
+                kept["verts"], kept["faces"], clean_info = eval_mesh.clean_pred(kept["verts"], kept["faces"], args,
+                                                                                 "hip")
+                print("%s: kept %d of %d components, %d of %d triangles" % (
+                    name, clean_info["n_components_kept"], clean_info["n_components"], clean_info["faces_kept"],
+                    n_tri), flush=True)
+                if args.write_clean_mesh:
+                    mesh.write_stl(os.path.join(out_dir, name + "_mesh_clean.stl"), kept["verts"], kept["faces"])
             if args.gt_mesh_dir is not None and backend != "hip":
                 print("eval: --gt_mesh_dir needs the hip mesh backend (auto chose %s); mesh metrics of %s skipped"
                       % (backend, name), file=sys.stderr)
@@ -198,7 +221,7 @@ def main(argv=None):
                 else:   # the device tensors, never the STL just written
                     pred = (eval_mesh.grid_to_world(kept["verts"], args.mesh_res), kept["faces"])
                     scores = eval_mesh.score_object(pred, gt_path, os.path.join(out_dir, eval_mesh.OUT_NAME), args,
-                                                    "hip")
+                                                    "hip", clean_info=clean_info)
                     print("%s: chamfer_l1 %.6g fscore %.4f normal_consistency %.4f%s" % (
                         name, scores["chamfer_l1"], scores["fscore"], scores["normal_consistency"],
                         " iou %.4f" % scores["iou"] if args.iou else ""), flush=True)

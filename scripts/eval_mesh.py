@@ -5,7 +5,8 @@ no counterpart: its eval/eval.py stops at the STL.
 
   python scripts/eval_mesh.py -O <eval output> -G <ground-truth dir> [--mesh_res 256] \
       [--normalize both|gt|none] [--gt_radius 1.0] [--n_samples 100000] [--tau 0.01] [--seed 0] \
-      [--iou] [--n_iou_points 100000] [--metrics_backend auto|hip|numpy] [--overwrite] [-R]
+      [--iou] [--n_iou_points 100000] [--components all|largest] [--min_component_frac F] \
+      [--metrics_backend auto|hip|numpy] [--overwrite] [-R]
 
 Map: every folder ``<object>`` of the output root that holds ``<object>_mesh.stl`` is paired with
 ``<ground-truth dir>/<object>.stl``; a missing ground truth skips the object with one line on
@@ -27,6 +28,16 @@ number against each mesh): ``mesh_metrics.txt`` gets the lines ``iou``, ``volume
 ``volume_gt`` and ``n_points`` after the others, and the reduce averages them too.  A contributing
 file without them (written by a run without --iou) stops the reduce with the object's name.  Without
 --iou both files are what they were.
+
+--components largest, or --min_component_frac F (0 < F <= 1; not both), cleans the PREDICTED mesh
+before it is scored (pnr.evaluate.clean_mesh; the ground truth is left as it is): the STL's soup is
+welded, its connected components are labelled, and only the component with the most faces, or every
+component with at least F times the faces of the largest, is kept.  This happens on the index-unit
+vertices, before they are mapped to the world cube and normalised, so a floater no longer moves the
+bounds the prediction is normalised by.  ``mesh_metrics.txt`` then ends with the lines
+``n_components``, ``n_components_kept`` and ``faces_kept``, and the reduce averages them; as with
+--iou, a contributing file without them stops the reduce with the object's name.  With both flags
+at their defaults every file is what it was.
 """
 import argparse
 import os
@@ -51,6 +62,36 @@ def add_mesh_metric_args(ap):
     ap.add_argument("--iou", action="store_true",
                     help="also score the volumetric IoU (winding-number containment) into mesh_metrics.txt")
     ap.add_argument("--n_iou_points", type=int, default=100000, help="uniform points of --iou")
+    ap.add_argument("--components", choices=("all", "largest"), default="all",
+                    help="largest = score only the predicted mesh's connected component with the most faces "
+                         "(welded first); all = every component")
+    ap.add_argument("--min_component_frac", type=float, default=None, metavar="F",
+                    help="keep the predicted mesh's components with at least F x the faces of the largest "
+                         "(0 < F <= 1; not with --components largest)")
+
+
+def component_args_error(args):
+    """The message for a bad combination of the cleanup flags, or None."""
+    if args.min_component_frac is not None:
+        if args.components == "largest":
+            return "--min_component_frac goes with --components all (largest keeps one component)"
+        if not 0.0 < args.min_component_frac <= 1.0:
+            return "--min_component_frac must be in (0, 1]"
+    return None
+
+
+def cleaning(args):
+    """Whether the predicted mesh is cleaned before it is scored."""
+    return args.components == "largest" or args.min_component_frac is not None
+
+
+def clean_pred(verts, faces, args, backend):
+    """The predicted mesh (index units) with its floaters dropped as the flags ask: (verts, faces,
+    info) of pnr.evaluate.clean_mesh on `backend`."""
+    from pnr import evaluate
+
+    return evaluate.clean_mesh(verts, faces, weld=True, keep=args.components, min_frac=args.min_component_frac,
+                               by="faces", backend=backend)
 
 
 def parse_args(argv=None):
@@ -85,10 +126,12 @@ def prepare_pair(pred_verts, gt_verts, args):
 
 
 def metric_names(args):
-    """The lines of a metrics file, in order: the surface scores, then with --iou the volume scores."""
+    """The lines of a metrics file, in order: the surface scores, then with --iou the volume scores,
+    then with a cleanup flag the component counts."""
     from pnr import evaluate
 
-    return tuple(evaluate.MESH_METRIC_NAMES) + (tuple(evaluate.VOLUME_METRIC_NAMES) if args.iou else ())
+    return (tuple(evaluate.MESH_METRIC_NAMES) + (tuple(evaluate.VOLUME_METRIC_NAMES) if args.iou else ())
+            + (tuple(evaluate.CLEAN_INFO_NAMES) if cleaning(args) else ()))
 
 
 def write_metrics(path, scores, names):
@@ -96,8 +139,9 @@ def write_metrics(path, scores, names):
         f.write("".join("{} {!r}\n".format(k, float(scores[k])) for k in names))
 
 
-def score_object(pred, gt_path, out_path, args, backend):
-    """pred = (verts in world units, faces); writes out_path, returns the scores."""
+def score_object(pred, gt_path, out_path, args, backend, clean_info=None):
+    """pred = (verts in world units, faces), already cleaned when a cleanup flag is set (clean_info:
+    clean_pred's info, whose counts then follow the scores); writes out_path, returns the scores."""
     from pnr import evaluate, mesh
 
     gv, gf = mesh.read_stl_indexed(gt_path)
@@ -107,6 +151,8 @@ def score_object(pred, gt_path, out_path, args, backend):
     if args.iou:
         scores.update(evaluate.volume_iou((pv, pred[1]), (gv, gf), n_points=args.n_iou_points, seed=args.seed,
                                           backend=backend))
+    if cleaning(args):
+        scores.update(clean_info)
     write_metrics(out_path, scores, metric_names(args))
     return scores
 
@@ -141,7 +187,10 @@ def run_map(args):
             print("eval_mesh: no ground truth %s; %s skipped" % (gt_path, name), file=sys.stderr)
             continue
         pv, pf = mesh.read_stl_indexed(stl)
-        score_object((grid_to_world(pv, args.mesh_res), pf), gt_path, out_path, args, backend)
+        info = None
+        if cleaning(args):   # on the index-unit soup, before the world map and the normalisation
+            pv, pf, info = clean_pred(pv, pf, args, backend)
+        score_object((grid_to_world(pv, args.mesh_res), pf), gt_path, out_path, args, backend, clean_info=info)
         done += 1
     print(">>> SCORED", done, "OBJECTS")
 
@@ -158,12 +207,20 @@ def run_reduce(args):
     if not folders:
         raise SystemExit("eval_mesh: no %s under %s" % (OUT_NAME, args.output))
     rows = [read_metrics(osp.join(args.output, x, OUT_NAME)) for x in folders]
+    from pnr import evaluate
+
     names = metric_names(args)
     if args.iou:
         for x, row in zip(folders, rows):
-            if any(name not in row for name in names):
+            if any(name not in row for name in evaluate.VOLUME_METRIC_NAMES):
                 raise SystemExit("eval_mesh: %s of object %s has no volume scores (scored without --iou; run the map "
                                  "again with --iou --overwrite)" % (OUT_NAME, x))
+    if cleaning(args):
+        for x, row in zip(folders, rows):
+            if any(name not in row for name in evaluate.CLEAN_INFO_NAMES):
+                raise SystemExit("eval_mesh: %s of object %s has no component counts (scored without --components / "
+                                 "--min_component_frac; run the map again with the flag and --overwrite)"
+                                 % (OUT_NAME, x))
     lines = []
     for name in names:
         acc = 0.0
@@ -184,6 +241,8 @@ def main(argv=None):
         raise SystemExit("eval_mesh: --mesh_res must be >= 2")
     if args.n_iou_points < 1:
         raise SystemExit("eval_mesh: --n_iou_points must be >= 1")
+    if component_args_error(args):
+        raise SystemExit("eval_mesh: " + component_args_error(args))
     if not args.reduce_only:
         print(">>> Compute")
         run_map(args)
