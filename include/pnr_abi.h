@@ -837,6 +837,91 @@ int pnr_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *
                             const int64_t *order, const int64_t *seg_start, int64_t n_components, double *out,
                             pnr_stream_t stream);
 
+/* ---- Mesh rendering (depth, silhouette and shaded views; additive in ABI 8) ---------------------
+ * The reference renders its training views of STL meshes with Blender scripts (headless_Blender.py,
+ * Blender_cli.py, newBlender.py); nothing of it runs on a device.  These calls render an indexed
+ * triangle mesh, verts (n_verts, 3) fp32 and faces (n_faces, 3) int32, from nv cameras at once:
+ * poses (nv, pose_rows, 4) fp32 with pose_rows 3 or 4, camera-to-world, x right, y up, the camera
+ * looking down -z (what pnr_gen_rays takes), and the host scalars w, h, fx, fy, cx, cy.
+ *
+ * Raster (pnr_mesh_raster): face (nv, h, w) int32, depth (nv, h, w) fp32.
+ *   Pixel     pixel (row j, column i) of view v is ray [v, j, i] of pnr_gen_rays: origin o = pose[:3, 3],
+ *             direction R u / |u| with u = (X, -Y, -1), X = fl(fl(i - cx) / fx), Y = fl(fl(j - cy) / fy),
+ *             |u| = sqrt(fl(fl(X X + Y Y) + 1)); integer pixel coordinates, no + 0.5.
+ *   Output    face = the nearest face the ray hits with t > 0, -1 where it hits none; depth = the
+ *             distance t along the UNIT direction (the quantity pnr_composite's depth is in), 0
+ *             where face is -1.
+ *   Camera    a vertex p goes to camera space as q = R^T (p - o): the three differences rounded
+ *             once, q_k = fma(R[2][k], d.z, fma(R[1][k], d.y, R[0][k] * d.x)).  R is taken for a
+ *             rotation: its transpose stands for its inverse, so an fp32 R that is orthonormal to
+ *             one rounding moves the depth by a few 1e-7 relative against the exact ray.
+ *   Edge      the edge p -> q of a face has the normal n = +-(lo x e), e = hi - lo (rounded once),
+ *             n.x = lo.y e.z - lo.z e.y, ... (two rounded products and one rounded difference, NO
+ *             fma), where lo is the endpoint whose WORLD coordinates come first in (x, y, z)
+ *             order and the sign is - when that is q.  The order is a rule of the endpoints alone,
+ *             so the face on the other side of the edge, in a welded mesh or an STL soup alike,
+ *             forms the same three floats and the opposite sign.
+ *   Hit       in homogeneous form, nothing is clipped.  E_k = fma(n_k.x, X, fma(n_k.y, -Y, -n_k.z))
+ *             for the edges ab, bc, ca (the signed volume u . (p x q); exactly opposite for the
+ *             two faces of an edge).  The ray hits the face when no two E_k have strictly opposite
+ *             signs (edges and vertices are included), det = (E_ab + E_bc) + E_ca is not 0 (the
+ *             face is not edge-on) and s = -(fma(E_ca, b.z, fma(E_bc, a.z, E_ab * c.z)) / det), the
+ *             camera-z depth of the hit point, is positive and finite.  Both orientations count.
+ *             A ray through a shared edge or vertex therefore hits at least one of the faces.  A
+ *             face that straddles the camera plane needs no special case.
+ *   Nearest   the smallest s wins, as computed in fp32; equal s go to the lower face index.
+ *             depth = s * |u|, rounded once.
+ *   Bad input a face with an index outside [0, n_verts), with a non-finite vertex or with zero area
+ *             (the unfused cross product of its two world edges is (0, 0, 0)) contributes nothing and
+ *             its vertices are never read through the bad index; a pose with a non-finite entry in
+ *             its first three rows makes that view all -1 / 0.
+ *   Result    a function of the inputs only: bit-identical from run to run, for a view alone or in
+ *             a batch, and with faces appended that cover no pixel; depth and face >= 0 are
+ *             bit-identical under any permutation of the faces.
+ *   Schedule  one lane per (view, face) computes the camera-space vertices, the edge normals and
+ *             the pixel bounds of the projected vertices (the whole image when a vertex is at or
+ *             behind the camera plane).  Bounds of at most PNR_RASTER_SMALL_PIXELS pixels are
+ *             scanned by the lane itself; larger faces are taken by the whole wave, PNR_RASTER_TILE
+ *             x PNR_RASTER_TILE pixels a step.  Both run the same arithmetic per (pixel, face).  The
+ *             workspace holds one 64-bit key (bits of s << 32 | face) per pixel, taken to its
+ *             minimum with an integer atomic; no float atomics.  pnr_mesh_raster_set_small moves
+ *             the threshold between the two paths for measurements (the result does not change).
+ *   Limits    w, h in 1 .. 8192; nv h w, n_faces and n_verts in 1 .. 2^31 - 1 (else the workspace
+ *             size is 0 and the call returns PNR_ERR_UNSUPPORTED).  No host sync, nothing allocated.
+ *
+ * Shading (pnr_mesh_shade): rgb (nv, h, w, 3) fp32, channels last, and optionally normal (nv, h, w, 3),
+ * from the face and depth of pnr_mesh_raster.  n = the unit normal (b - a) x (c - a) of the face,
+ * negated where n . d > 0 for the pixel's unit direction d (turned towards the camera, two-sided);
+ * p = o + depth d; rgb = clamp(albedo * (ambient + sum_l k_l max(0, n . unit(L_l - p))), 0, 254/255), so
+ * no object pixel is the 255-white a loader reads as background.  Up to PNR_RASTER_MAX_LIGHTS point
+ * lights: lights (n_lights, 3) world positions and weights (n_lights) are HOST arrays, as are albedo
+ * (3) and background (3), read during the call.  A pixel whose face is outside [0, n_faces) gets the
+ * background triple and the normal (0, 0, 0). */
+#define PNR_RASTER_BLOCK 256        /* (view, face) lanes per workgroup of the coverage kernel */
+#define PNR_RASTER_TILE 8           /* the wave tests TILE x TILE pixels of a large face a step */
+#define PNR_RASTER_SMALL_PIXELS 8   /* bounds of at most this many pixels are scanned by one lane */
+#define PNR_RASTER_MAX_LIGHTS 8
+
+/* Workspace bytes of pnr_mesh_raster (the keys, 8 bytes per pixel); 0 for an unsupported shape. */
+size_t pnr_mesh_raster_workspace_bytes(int64_t nv, int32_t h, int32_t w, int64_t n_faces);
+
+/* workspace 8-byte aligned.  Stream-ordered, no host sync. */
+int pnr_mesh_raster(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *poses,
+                    int64_t nv, int32_t pose_rows, int32_t w, int32_t h, float fx, float fy, float cx, float cy,
+                    void *workspace, size_t workspace_bytes, int32_t *face_out, float *depth_out,
+                    pnr_stream_t stream);
+
+/* The largest pixel count a lane scans on its own (default PNR_RASTER_SMALL_PIXELS; negative restores
+ * it); returns the previous value.  Process-wide, for measurements: outputs do not depend on it. */
+int pnr_mesh_raster_set_small(int32_t pixels);
+
+/* normal may be NULL.  lights / weights may be NULL when n_lights is 0. */
+int pnr_mesh_shade(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *poses,
+                   int64_t nv, int32_t pose_rows, int32_t w, int32_t h, float fx, float fy, float cx, float cy,
+                   const int32_t *face, const float *depth, const float *lights, const float *weights,
+                   int32_t n_lights, const float *albedo, float ambient, const float *background, float *rgb,
+                   float *normal, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

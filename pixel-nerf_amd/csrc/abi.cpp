@@ -22,6 +22,8 @@ static thread_local char g_err[1024];
 // Set once at start-up by callers that want another default; a call naming its own mode never
 // reads it.
 static std::atomic<int> g_fused_default{2};
+// pnr_mesh_raster_set_small: the largest pixel count one lane scans (-1: PNR_RASTER_SMALL_PIXELS)
+static std::atomic<int> g_raster_small{-1};
 
 int fail(int status, const char *fmt, ...) {
     va_list ap;
@@ -829,6 +831,52 @@ int pnr_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *
                     "pnr_mesh_component_sums: verts and faces must be 4-byte, order, seg_start and out 8-byte aligned");
     return launch_mesh_component_sums(verts, n_verts, faces, n_faces, order, seg_start, n_components, out,
                                       (hipStream_t)stream);
+}
+
+size_t pnr_mesh_raster_workspace_bytes(int64_t nv, int32_t h, int32_t w, int64_t n_faces) {
+    return mesh_raster_workspace_bytes(nv, h, w, n_faces);
+}
+
+int pnr_mesh_raster_set_small(int32_t pixels) {
+    const int prev = g_raster_small.exchange(pixels < 0 ? -1 : pixels);
+    return prev < 0 ? PNR_RASTER_SMALL_PIXELS : prev;
+}
+
+int pnr_mesh_raster(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *poses,
+                    int64_t nv, int32_t pose_rows, int32_t w, int32_t h, float fx, float fy, float cx, float cy,
+                    void *workspace, size_t workspace_bytes, int32_t *face_out, float *depth_out,
+                    pnr_stream_t stream) {
+    if (nv < 1 || n_faces < 1 || n_verts < 1 || w < 1 || h < 1)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_raster: nv, n_faces, n_verts, w and h must be >= 1");
+    if (pose_rows != 3 && pose_rows != 4)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_raster: pose_rows must be 3 or 4 (got %d)", pose_rows);
+    if (!verts || !faces || !poses || !face_out || !depth_out)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_raster: NULL argument");
+    if (misaligned(3, verts, faces, poses, face_out, depth_out))
+        return fail(PNR_ERR_INVALID, "pnr_mesh_raster: verts, faces, poses, face and depth must be 4-byte aligned");
+    if (misaligned(7, workspace)) return fail(PNR_ERR_INVALID, "pnr_mesh_raster: workspace must be 8-byte aligned");
+    return launch_mesh_raster(verts, n_verts, faces, n_faces, poses, nv, pose_rows, w, h, fx, fy, cx, cy, workspace,
+                              workspace_bytes, face_out, depth_out, g_raster_small.load(std::memory_order_relaxed),
+                              (hipStream_t)stream);
+}
+
+int pnr_mesh_shade(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *poses,
+                   int64_t nv, int32_t pose_rows, int32_t w, int32_t h, float fx, float fy, float cx, float cy,
+                   const int32_t *face, const float *depth, const float *lights, const float *weights,
+                   int32_t n_lights, const float *albedo, float ambient, const float *background, float *rgb,
+                   float *normal, pnr_stream_t stream) {
+    if (nv < 1 || n_faces < 1 || n_verts < 1 || w < 1 || h < 1)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_shade: nv, n_faces, n_verts, w and h must be >= 1");
+    if (pose_rows != 3 && pose_rows != 4)
+        return fail(PNR_ERR_INVALID, "pnr_mesh_shade: pose_rows must be 3 or 4 (got %d)", pose_rows);
+    if (!verts || !faces || !poses || !face || !depth || !albedo || !background || !rgb ||
+        (n_lights > 0 && (!lights || !weights)))
+        return fail(PNR_ERR_INVALID, "pnr_mesh_shade: NULL argument");
+    if (misaligned(3, verts, faces, poses, face, depth, rgb, normal))
+        return fail(PNR_ERR_INVALID,
+                    "pnr_mesh_shade: verts, faces, poses, face, depth, rgb and normal must be 4-byte aligned");
+    return launch_mesh_shade(verts, n_verts, faces, n_faces, poses, nv, pose_rows, w, h, fx, fy, cx, cy, face, depth,
+                             lights, weights, n_lights, albedo, ambient, background, rgb, normal, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -117,5 +117,15 @@ int launch_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_vert
 int launch_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
                                const int64_t *order, const int64_t *seg_start, int64_t n_components, double *out,
                                hipStream_t st);
+// meshraster.hip (small_max < 0: PNR_RASTER_SMALL_PIXELS)
+size_t mesh_raster_workspace_bytes(int64_t nv, int h, int w, int64_t n_faces);
+int launch_mesh_raster(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *poses,
+                       int64_t nv, int pose_rows, int w, int h, float fx, float fy, float cx, float cy, void *ws,
+                       size_t bytes, int32_t *face_out, float *depth_out, int small_max, hipStream_t st);
+int launch_mesh_shade(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *poses,
+                      int64_t nv, int pose_rows, int w, int h, float fx, float fy, float cx, float cy,
+                      const int32_t *face_in, const float *depth_in, const float *lights, const float *weights,
+                      int n_lights, const float albedo[3], float ambient, const float background[3], float *rgb,
+                      float *normal, hipStream_t st);
 
 }  // namespace pnr

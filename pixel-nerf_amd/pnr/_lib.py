@@ -165,6 +165,14 @@ SIGNATURES = {
     "pnr_mesh_components_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pnr_mesh_components": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_size, c_vp, c_vp, ctypes.POINTER(c_i32), c_vp]),
     "pnr_mesh_component_sums": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    # mesh rendering (csrc/meshraster.hip); face int32, depth / rgb / normal float32; lights, weights,
+    # albedo and background of pnr_mesh_shade are host float arrays
+    "pnr_mesh_raster_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i64]),
+    "pnr_mesh_raster": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f,
+                                c_vp, c_size, c_vp, c_vp, c_vp]),
+    "pnr_mesh_raster_set_small": (c_i32, [c_i32]),
+    "pnr_mesh_shade": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f,
+                               c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_f, c_vp, c_vp, c_vp, c_vp]),
 }
 
 # pnr_weight_grad_arith arithmetics (PNR_WGRAD_*, ABI 4)

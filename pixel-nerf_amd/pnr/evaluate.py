@@ -20,7 +20,8 @@ from . import util
 __all__ = ["ssim", "psnr_np", "image_metrics", "select_views", "eval_approx", "mesh_metrics", "sample_mesh_np",
            "nearest_np", "MESH_METRIC_NAMES", "volume_iou", "winding_np", "box_sample_np",
            "VOLUME_METRIC_NAMES", "clean_mesh", "weld_np", "components_np", "component_stats_np",
-           "CLEAN_INFO_NAMES"]
+           "CLEAN_INFO_NAMES", "sphere_poses", "raycast_np", "shade_np", "render_mesh_views", "silhouette_scores",
+           "SIL_METRIC_NAMES", "ssaa_camera"]
 
 
 def psnr_np(pred, target, data_range=1.0):
@@ -623,3 +624,263 @@ def clean_mesh(verts, faces, weld=True, keep="largest", min_frac=None, by="faces
         out_f = (torch.cumsum(used, 0, dtype=torch.int64) - 1)[faces_k.long()].to(torch.int32).reshape(-1, 3)
     return out_v, out_f, {"n_components": n_comp, "n_components_kept": int(sel.sum()),
                           "faces_kept": int(out_f.shape[0])}
+
+
+# ---- mesh rendering: cameras, the host ray cast, views of a mesh, silhouette scores ----------------
+SIL_METRIC_NAMES = ("sil_iou", "sil_depth_l1", "sil_views")
+_FILE_FLIP = np.diag([1.0, -1.0, -1.0, 1.0])
+
+
+def sphere_poses(n_views, radius, hemisphere=True):
+    """The cameras of the reference's Blender scripts: points of a golden spiral on the sphere of
+    ``radius`` (point i of N: azimuth 2 pi i / golden ratio, polar angle arccos(1 - 2 (i + 0.5) / N)),
+    each looking at the origin with the world's z axis up.  ``hemisphere`` takes N = 2 n_views points
+    and keeps the upper half (the first n_views), else N = n_views over the whole sphere.  Returns
+    ``(poses, file_poses)``, both (n_views, 4, 4) float64 camera-to-world: ``poses`` in the loader's
+    convention (x right, y up, looking down -z: what SRNDataset returns and gen_rays takes) and
+    ``file_poses`` as the pose files hold them; they differ by the diag(1, -1, -1, 1) the loader
+    applies on the right."""
+    n_views = int(n_views)
+    if n_views < 1:
+        raise ValueError("sphere_poses: n_views must be >= 1 (got %d)" % n_views)
+    n = 2 * n_views if hemisphere else n_views
+    i = np.arange(n, dtype=np.float64)
+    theta = 2.0 * np.pi * i / ((1.0 + 5.0 ** 0.5) / 2.0)
+    phi = np.arccos(1.0 - 2.0 * (i + 0.5) / n)
+    pos = float(radius) * np.stack([np.cos(theta) * np.sin(phi), np.sin(theta) * np.sin(phi), np.cos(phi)], -1)
+    pos = pos[:n_views]
+    z = pos / np.linalg.norm(pos, axis=1, keepdims=True)          # the camera looks down -z, at the origin
+    x = np.cross(np.array([0.0, 0.0, 1.0]), z)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    y = np.cross(z, x)
+    poses = np.tile(np.eye(4), (n_views, 1, 1))
+    poses[:, :3, 0], poses[:, :3, 1], poses[:, :3, 2], poses[:, :3, 3] = x, y, z, pos
+    return poses, poses @ _FILE_FLIP
+
+
+def ssaa_camera(k, fx, fy, cx, cy):
+    """(fx, fy, cx, cy) of the k x supersampled image whose k x k blocks are centred on the pixels'
+    rays: fx k, fy k, cx k + (k - 1) / 2, cy k + (k - 1) / 2."""
+    return fx * k, fy * k, cx * k + (k - 1) / 2.0, cy * k + (k - 1) / 2.0
+
+
+def _np_mesh(verts, faces):
+    v, f = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (verts, faces))
+    return np.ascontiguousarray(v, np.float32).reshape(-1, 3), np.ascontiguousarray(f, np.int64).reshape(-1, 3)
+
+
+def _np_poses(poses):
+    p = poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses)
+    p = np.ascontiguousarray(p, np.float32).astype(np.float64)
+    if p.ndim != 3 or p.shape[1] not in (3, 4) or p.shape[2] != 4:
+        raise ValueError("poses must be (NV, 4, 4) or (NV, 3, 4) (got %s)" % (p.shape,))
+    return p
+
+
+def _pixel_dirs(width, height, fx, fy, cx, cy):
+    """(X, -Y) of every pixel's direction (X, -Y, -1), (H W,) each, from the fp32 camera scalars."""
+    fx, fy, cx, cy = (float(np.float32(t)) for t in (fx, fy, cx, cy))
+    jj, ii = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing="ij")
+    return ((ii - cx) / fx).reshape(-1), (-(jj - cy) / fy).reshape(-1)
+
+
+def raycast_np(verts, faces, poses, width, height, focal, c=None, chunk=None):
+    """pnr_mesh_raster's rule on the host (include/pnr_abi.h, "Mesh rendering"): ``(face (NV, H, W)
+    int32, depth (NV, H, W) float64)`` by brute force over all pixels x faces in fp64 on the fp32
+    inputs, ``chunk`` pixels at a time (default: about 2^21 pairs per step).  The same homogeneous hit
+    rule (no two edge volumes of strictly opposite signs, not edge-on, depth > 0), the smallest
+    camera-z depth wins and equal depths go to the lower face; faces with an index outside [0, V),
+    a non-finite vertex or zero area, and views with a non-finite pose, contribute nothing."""
+    from . import util
+
+    v, f = _np_mesh(verts, faces)
+    p = _np_poses(poses)
+    width, height = int(width), int(height)
+    fx, fy, cx, cy = util._focal_c(width, height, focal, c)
+    X, Yn = _pixel_dirs(width, height, fx, fy, cx, cy)
+    length = np.sqrt(X * X + Yn * Yn + 1.0)
+    nv, hw = p.shape[0], width * height
+    face = np.full((nv, hw), -1, np.int32)
+    depth = np.zeros((nv, hw))
+    ok = ((f >= 0) & (f < len(v))).all(1) if len(v) else np.zeros(len(f), bool)
+    ids = np.nonzero(ok)[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        tri = v.astype(np.float64)[f[ids]]                               # (T, 3, 3)
+        area = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+        good = np.isfinite(tri).all((1, 2)) & (area != 0).any(1) & np.isfinite(area).all(1)
+    ids, tri = ids[good], tri[good]
+    if len(ids) == 0:
+        return face.reshape(nv, height, width), depth.reshape(nv, height, width)
+    chunk = chunk or max(1, (1 << 21) // len(ids))
+    for k in range(nv):
+        if not np.isfinite(p[k, :3]).all():
+            continue
+        try:   # R^-1 (v - o), rows: the device takes the fp32 R for a rotation and uses R^T
+            cam = (tri - p[k, :3, 3]) @ np.linalg.inv(p[k, :3, :3]).T
+        except np.linalg.LinAlgError:
+            continue
+        a, b, cc = cam[:, 0], cam[:, 1], cam[:, 2]
+        n_ab, n_bc, n_ca = np.cross(a, b), np.cross(b, cc), np.cross(cc, a)
+        for i in range(0, hw, chunk):
+            x, y = X[i:i + chunk, None], Yn[i:i + chunk, None]
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                e_ab = x * n_ab[:, 0] + y * n_ab[:, 1] - n_ab[:, 2]
+                e_bc = x * n_bc[:, 0] + y * n_bc[:, 1] - n_bc[:, 2]
+                e_ca = x * n_ca[:, 0] + y * n_ca[:, 1] - n_ca[:, 2]
+                pos = (e_ab > 0) | (e_bc > 0) | (e_ca > 0)
+                neg = (e_ab < 0) | (e_bc < 0) | (e_ca < 0)
+                det = e_ab + e_bc + e_ca
+                s = -(e_bc * a[:, 2] + e_ca * b[:, 2] + e_ab * cc[:, 2]) / det
+                hit = ~(pos & neg) & (det != 0) & (s > 0) & np.isfinite(s)
+            s = np.where(hit, s, np.inf)
+            best = s.argmin(1)                                          # the first minimum: the lowest face
+            sb = s[np.arange(len(best)), best]
+            got = np.isfinite(sb)
+            face[k, i:i + chunk] = np.where(got, ids[best], -1)
+            depth[k, i:i + chunk] = np.where(got, sb * length[i:i + chunk], 0.0)
+    return face.reshape(nv, height, width), depth.reshape(nv, height, width)
+
+
+def shade_np(verts, faces, poses, width, height, focal, face, depth, c=None, lights=(), weights=(),
+             albedo=(0.8, 0.8, 0.8), ambient=0.2, background=(1.0, 1.0, 1.0)):
+    """pnr_mesh_shade's formula in fp64 on the host: ``(rgb (NV, H, W, 3), normal (NV, H, W, 3))``
+    float64 from the face and depth of a raster (include/pnr_abi.h, "Mesh rendering", Shading)."""
+    from . import util
+
+    v, f = _np_mesh(verts, faces)
+    p = _np_poses(poses)
+    width, height = int(width), int(height)
+    fx, fy, cx, cy = util._focal_c(width, height, focal, c)
+    X, Yn = _pixel_dirs(width, height, fx, fy, cx, cy)
+    u = np.stack([X, Yn, -np.ones_like(X)], -1)
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    face = np.asarray(face).reshape(p.shape[0], -1)
+    depth = np.asarray(depth, np.float64).reshape(p.shape[0], -1)
+    rgb = np.empty(face.shape + (3,))
+    normal = np.zeros(face.shape + (3,))
+    rgb[:] = np.asarray(background, np.float64)
+    for k in range(p.shape[0]):
+        m = face[k] >= 0
+        if not m.any():
+            continue
+        tri = v.astype(np.float64)[f[face[k][m]]]
+        d = u[m] @ p[k, :3, :3].T
+        pt = p[k, :3, 3] + depth[k][m, None] * d
+        n = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+        n /= np.linalg.norm(n, axis=1, keepdims=True)
+        n = np.where(((n * d).sum(1) > 0)[:, None], -n, n)
+        lum = np.full(len(n), float(ambient))
+        for L, w in zip(lights, weights):
+            to = np.asarray(L, np.float64) - pt
+            with np.errstate(invalid="ignore", divide="ignore"):
+                cos = (n * to).sum(1) / np.linalg.norm(to, axis=1)
+            lum += float(w) * np.where(cos > 0, cos, 0.0)
+        rgb[k][m] = np.clip(np.asarray(albedo, np.float64) * lum[:, None], 0.0, 254.0 / 255.0)
+        normal[k][m] = n
+    shape = (p.shape[0], height, width, 3)
+    return rgb.reshape(shape), normal.reshape(shape)
+
+
+def _raster_backend(backend):
+    if backend == "auto":
+        backend = "hip" if torch.cuda.is_available() else "numpy"
+    if backend not in ("hip", "numpy"):
+        raise ValueError("render backend must be 'auto', 'numpy' or 'hip' (got %r)" % (backend,))
+    return backend
+
+
+def _raster(verts, faces, poses, width, height, fx, fy, cx, cy, backend):
+    """(face, depth) on `backend`: device tensors from hip, arrays from numpy."""
+    if backend == "numpy":
+        return raycast_np(verts, faces, poses, width, height, (fx, fy), (cx, cy))
+    from . import ops
+
+    return ops.mesh_raster(verts, faces, poses, width, height, (fx, fy), (cx, cy))
+
+
+def _to_device(verts, faces, poses):
+    dev = next((t.device for t in (verts, faces, poses) if torch.is_tensor(t) and t.device.type == "cuda"),
+               torch.device("cuda", torch.cuda.current_device()))
+
+    def on_dev(t, dtype):
+        t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+        return t.to(device=dev, dtype=dtype).contiguous()
+
+    return on_dev(verts, torch.float32).reshape(-1, 3), on_dev(faces, torch.int32).reshape(-1, 3), on_dev(
+        poses, torch.float32)
+
+
+def render_mesh_views(verts, faces, poses, width, height, focal, c=None, ssaa=1, backend="auto", **shading):
+    """Shaded views of a mesh from a batch of cameras: a dict with ``rgb`` (NV, H, W, 3) float32 in
+    [0, 1], ``mask`` (NV, H, W) float32 (the covered share of each pixel) and ``face`` / ``depth`` of
+    the raster itself, (NV, k H, k W).  ``ssaa = k`` renders at k times the size with the camera
+    ``ssaa_camera`` gives, whose k x k samples are centred on the pixel's ray, and box-averages the
+    blocks of ``rgb`` and of the mask in torch.  ``shading``: the keyword arguments of
+    ``ops.mesh_shade`` (lights, weights, albedo, ambient, background).  ``"hip"`` runs pnr.ops.mesh_raster
+    / mesh_shade on the device the inputs are on (host inputs are moved to the current HIP device) and
+    returns device tensors; ``"numpy"`` runs ``raycast_np`` / ``shade_np`` on the host and returns host
+    tensors; ``"auto"`` is hip where a HIP device is present."""
+    from . import util
+
+    backend = _raster_backend(backend)
+    k = int(ssaa)
+    if k < 1:
+        raise ValueError("render_mesh_views: ssaa must be >= 1 (got %d)" % k)
+    width, height = int(width), int(height)
+    fx, fy, cx, cy = ssaa_camera(k, *util._focal_c(width, height, focal, c))
+    w, h = width * k, height * k
+    if backend == "numpy":
+        face, depth = raycast_np(verts, faces, poses, w, h, (fx, fy), (cx, cy))
+        rgb, _ = shade_np(verts, faces, poses, w, h, (fx, fy), face, depth, c=(cx, cy), **shading)
+        face, depth, rgb = torch.from_numpy(face), torch.from_numpy(depth).float(), torch.from_numpy(rgb).float()
+    else:
+        from . import ops
+
+        verts, faces, poses = _to_device(verts, faces, poses)
+        face, depth = ops.mesh_raster(verts, faces, poses, w, h, (fx, fy), (cx, cy))
+        rgb, _ = ops.mesh_shade(verts, faces, poses, w, h, (fx, fy), face, depth, c=(cx, cy), **shading)
+    mask = (face >= 0).float()
+    if k > 1:
+        nv = rgb.shape[0]
+        rgb = rgb.reshape(nv, height, k, width, k, 3).mean(dim=(2, 4))
+        mask = mask.reshape(nv, height, k, width, k).mean(dim=(2, 4))
+    return {"rgb": rgb, "mask": mask, "face": face, "depth": depth}
+
+
+def silhouette_scores(pred, gt, poses, width, height, focal, c=None, backend="auto"):
+    """The 2D scores of single-view reconstruction work: a predicted mesh against a ground-truth
+    mesh, each a ``(verts, faces)`` pair of tensors or arrays, both seen from ``poses``.  Returns a
+    dict of floats (SIL_METRIC_NAMES): ``sil_iou`` = the mean over the views of |A and B| / |A or B|
+    of the two silhouettes (a view where both are empty counts 1), ``sil_depth_l1`` = the mean
+    |depth_pred - depth_gt| over the pixels of all views that both cover (+inf when there is none),
+    ``sil_views`` = the number of views.  A predicted mesh without faces is a result (it covers
+    nothing); an empty ground truth raises.  Backends as in ``render_mesh_views``."""
+    from . import util
+
+    backend = _raster_backend(backend)
+    (pv, pf), (gv, gf) = pred, gt
+    if len(gf) == 0:
+        raise ValueError("silhouette_scores: the ground-truth mesh has no faces")
+    width, height = int(width), int(height)
+    fx, fy, cx, cy = util._focal_c(width, height, focal, c)
+    if backend == "hip":
+        gv, gf, poses = _to_device(gv, gf, poses)
+        if len(pf):
+            pv, pf, _ = _to_device(pv, pf, poses)
+    nv = int(poses.shape[0])
+    face_g, depth_g = _raster(gv, gf, poses, width, height, fx, fy, cx, cy, backend)
+    if len(pf):
+        face_p, depth_p = _raster(pv, pf, poses, width, height, fx, fy, cx, cy, backend)
+    else:
+        face_p, depth_p = face_g * 0 - 1, depth_g * 0
+    if backend == "numpy":
+        face_p, depth_p, face_g, depth_g = (torch.from_numpy(np.ascontiguousarray(t))
+                                            for t in (face_p, depth_p, face_g, depth_g))
+    a, b = (face_p >= 0).reshape(nv, -1), (face_g >= 0).reshape(nv, -1)
+    inter, union = (a & b).sum(1).double(), (a | b).sum(1).double()
+    iou = torch.where(union > 0, inter / union.clamp(min=1.0), torch.ones_like(union)).mean()
+    both = (a & b).reshape(depth_p.shape)
+    err = ((depth_p.double() - depth_g.double()).abs() * both).sum()
+    out = torch.stack([iou, err, inter.sum()]).cpu().tolist()   # the one read-back
+    return {"sil_iou": out[0], "sil_depth_l1": out[1] / out[2] if out[2] > 0 else float("inf"),
+            "sil_views": float(nv)}

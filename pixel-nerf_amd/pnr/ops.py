@@ -389,6 +389,136 @@ def box_sample(lo, hi, n, seed=0, device="cuda"):
     return points
 
 
+# constants of pnr_mesh_raster (PNR_RASTER_*, include/pnr_abi.h): (view, face) lanes per workgroup,
+# the side of the pixel block a wave tests per step of a large face, the largest pixel bounds one
+# lane scans on its own, the most point lights of pnr_mesh_shade
+RASTER_BLOCK = 256
+RASTER_TILE = 8
+RASTER_SMALL_PIXELS = 8
+RASTER_MAX_LIGHTS = 8
+
+
+def _raster_args(verts, faces, poses, width, height, focal, c):
+    from . import util
+
+    verts = _cloud(verts, "verts")
+    faces = _cloud(faces, "faces", torch.int32)
+    if not torch.is_tensor(poses):
+        raise TypeError("poses must be a tensor")
+    if poses.device.type != "cuda":
+        raise ValueError("pnr: poses must be on a HIP device (got %s); the HIP path has no CPU "
+                         "fallback" % (poses.device,))
+    if poses.dtype != torch.float32:
+        raise ValueError("pnr: poses must be float32 (got %s)" % (poses.dtype,))
+    if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+        raise ValueError("pnr: poses must be (NV, 4, 4) or (NV, 3, 4) (got %s)" % (tuple(poses.shape),))
+    poses = poses.contiguous()
+    for t, name in ((faces, "faces"), (poses, "poses")):
+        if t.device != verts.device:
+            raise ValueError("pnr: %s is on %s, verts on %s" % (name, t.device, verts.device))
+    nv, n_v, n_t = int(poses.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    if nv < 1:
+        raise ValueError("pnr: poses must hold at least one view (got %d)" % nv)
+    if n_v < 1 or n_t < 1:
+        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) renders nothing" % (n_v, n_t))
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("pnr: width and height must be >= 1 (got %d, %d)" % (width, height))
+    fx, fy, cx, cy = util._focal_c(width, height, focal, c)
+    return verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy
+
+
+def mesh_raster(verts, faces, poses, width, height, focal, c=None):
+    """Nearest face and depth of an indexed device mesh for every pixel of a batch of cameras
+    (include/pnr_abi.h, "Mesh rendering"; csrc/meshraster.hip): verts (V, 3) float32, faces (T, 3)
+    int32, poses (NV, 4, 4) or (NV, 3, 4) float32 camera-to-world in the loader's convention ->
+    ``(face (NV, H, W) int32, depth (NV, H, W) float32)``.  Pixel [v, j, i] is ray [v, j, i] of
+    ``util.gen_rays(poses, width, height, focal, ., ., c)``; ``face`` is -1 and ``depth`` 0 where the
+    ray hits nothing, else ``depth`` is the distance along the unit direction (the composite's
+    depth).  Both are functions of the inputs alone, bit for bit.  No host sync."""
+    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy = _raster_args(verts, faces, poses, width, height,
+                                                                                    focal, c)
+    lib = _lib.load()
+    dev = verts.device
+    nbytes = lib.pnr_mesh_raster_workspace_bytes(nv, height, width, n_t)
+    if nbytes == 0 or n_v >= 2 ** 31:
+        raise _lib.PnrError("pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
+                            "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    face = torch.empty(nv, height, width, device=dev, dtype=torch.int32)
+    depth = torch.empty(nv, height, width, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mesh_raster(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(poses), nv,
+                                       int(poses.shape[1]), width, height, fx, fy, cx, cy, _lib.ptr(ws), nbytes,
+                                       _lib.ptr(face), _lib.ptr(depth), _lib.stream_of(dev)), "pnr_mesh_raster")
+    return face, depth
+
+
+class raster_small_pixels:
+    """Context manager: pnr_mesh_raster_set_small(pixels) inside, the previous value restored after.
+    It moves the threshold between the lane path and the wave path of ``mesh_raster`` (measurements
+    and tests; the outputs do not depend on it)."""
+
+    def __init__(self, pixels):
+        self.pixels = int(pixels)
+
+    def __enter__(self):
+        self.prev = _lib.load().pnr_mesh_raster_set_small(self.pixels)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.load().pnr_mesh_raster_set_small(self.prev)
+        return False
+
+
+def mesh_shade(verts, faces, poses, width, height, focal, face, depth, c=None, lights=(), weights=(),
+               albedo=(0.8, 0.8, 0.8), ambient=0.2, background=(1.0, 1.0, 1.0), want_normal=False):
+    """Flat-shaded colour of ``mesh_raster``'s pixels (include/pnr_abi.h, "Mesh rendering", Shading):
+    ``rgb (NV, H, W, 3) float32`` channels-last (the layout ``image_metrics`` takes), and with
+    ``want_normal`` the unit face normals turned towards the camera ``(NV, H, W, 3)`` (else None).
+    ``lights``: up to RASTER_MAX_LIGHTS world positions (triples), ``weights`` one float each;
+    ``albedo`` and ``background`` triples; colours of covered pixels are clamped to [0, 254/255]."""
+    import ctypes
+
+    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy = _raster_args(verts, faces, poses, width, height,
+                                                                                    focal, c)
+    dev = verts.device
+    for t, name, dtype in ((face, "face", torch.int32), (depth, "depth", torch.float32)):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+        if t.device != dev:
+            raise ValueError("pnr: %s is on %s, verts on %s" % (name, t.device, dev))
+        if t.dtype != dtype:
+            raise ValueError("pnr: %s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
+        if tuple(t.shape) != (nv, height, width):
+            raise ValueError("pnr: %s must be %s (got %s)" % (name, (nv, height, width), tuple(t.shape)))
+    lights = [[float(x) for x in l] for l in lights]
+    weights = [float(x) for x in weights]
+    if len(lights) != len(weights) or len(lights) > RASTER_MAX_LIGHTS or any(len(l) != 3 for l in lights):
+        raise ValueError("pnr: lights must be at most %d triples with one weight each (got %d lights, %d weights)"
+                         % (RASTER_MAX_LIGHTS, len(lights), len(weights)))
+    albedo, background = [float(x) for x in albedo], [float(x) for x in background]
+    if len(albedo) != 3 or len(background) != 3:
+        raise ValueError("pnr: albedo and background must be triples")
+    lib = _lib.load()
+    if lib.pnr_mesh_raster_workspace_bytes(nv, height, width, n_t) == 0 or n_v >= 2 ** 31:
+        raise _lib.PnrError("pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
+                            "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
+    n_l = len(lights)
+    c_l = (ctypes.c_float * max(1, 3 * n_l))(*[x for l in lights for x in l])
+    c_w = (ctypes.c_float * max(1, n_l))(*weights)
+    c_a, c_b = (ctypes.c_float * 3)(*albedo), (ctypes.c_float * 3)(*background)
+    rgb = torch.empty(nv, height, width, 3, device=dev, dtype=torch.float32)
+    normal = torch.empty(nv, height, width, 3, device=dev, dtype=torch.float32) if want_normal else None
+    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)   # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_mesh_shade(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(poses), nv,
+                                      int(poses.shape[1]), width, height, fx, fy, cx, cy, _lib.ptr(face.contiguous()),
+                                      _lib.ptr(depth.contiguous()), vp(c_l), vp(c_w), n_l, vp(c_a), float(ambient),
+                                      vp(c_b), _lib.ptr(rgb), _lib.ptr(normal), _lib.stream_of(dev)), "pnr_mesh_shade")
+    return rgb, normal
+
+
 # workgroup size of the weld / component kernels (PNR_MESH_CLEAN_BLOCK, include/pnr_abi.h): one
 # thread per vertex or face, so sizes around a multiple of it exercise the partial last workgroup
 MESH_CLEAN_BLOCK = 256

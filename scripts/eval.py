@@ -32,7 +32,10 @@ object without a ground-truth file is skipped with one line on stderr.  --compon
 is scored (pnr.evaluate.clean_mesh: pnr.ops.mesh_weld / mesh_components / mesh_component_stats,
 csrc/meshclean.hip) and add the component counts to mesh_metrics.txt; --write_clean_mesh also writes
 the cleaned mesh as <output>/<object>/<object>_mesh_clean.stl beside the untouched
-<object>_mesh.stl."""
+<object>_mesh.stl.  --sil_views N (with --sil_size / --sil_focal; scripts/eval_mesh.py's flags, off by
+default) renders the pair as it is scored from N cameras around it (pnr.evaluate.silhouette_scores:
+pnr.ops.mesh_raster, csrc/meshraster.hip) and ends mesh_metrics.txt with sil_iou, sil_depth_l1 and
+sil_views."""
 import argparse
 import os
 import sys
@@ -148,6 +151,8 @@ def main(argv=None):
         ap.error("--gt_mesh_dir scores the device mesh: it needs --mesh_backend hip (or auto without skimage)")
     if eval_mesh.component_args_error(args):
         ap.error(eval_mesh.component_args_error(args))
+    if eval_mesh.sil_args_error(args):
+        ap.error(eval_mesh.sil_args_error(args))
     if args.write_clean_mesh and not eval_mesh.cleaning(args):
         ap.error("--write_clean_mesh needs --components largest or --min_component_frac")
     if args.write_clean_mesh and args.mesh_backend == "skimage":

@@ -6,6 +6,7 @@ no counterpart: its eval/eval.py stops at the STL.
   python scripts/eval_mesh.py -O <eval output> -G <ground-truth dir> [--mesh_res 256] \
       [--normalize both|gt|none] [--gt_radius 1.0] [--n_samples 100000] [--tau 0.01] [--seed 0] \
       [--iou] [--n_iou_points 100000] [--components all|largest] [--min_component_frac F] \
+      [--sil_views N] [--sil_size 128] [--sil_focal 131.25] \
       [--metrics_backend auto|hip|numpy] [--overwrite] [-R]
 
 Map: every folder ``<object>`` of the output root that holds ``<object>_mesh.stl`` is paired with
@@ -38,6 +39,16 @@ bounds the prediction is normalised by.  ``mesh_metrics.txt`` then ends with the
 ``n_components``, ``n_components_kept`` and ``faces_kept``, and the reduce averages them; as with
 --iou, a contributing file without them stops the reduce with the object's name.  With both flags
 at their defaults every file is what it was.
+
+--sil_views N (default 0: off) adds the 2D scores of single-view reconstruction work
+(pnr.evaluate.silhouette_scores; pnr.ops.mesh_raster, csrc/meshraster.hip, with the hip backend): the
+pair as it is scored, after normalisation and cleanup, is rendered from the N cameras of
+pnr.evaluate.sphere_poses at --sil_size pixels with the focal length --sil_focal, at the radius from
+which a sphere of radius 1.05 fills that field of view (so a pair normalised to the unit sphere is
+seen whole).  ``mesh_metrics.txt`` then ends with the lines ``sil_iou`` (the mean silhouette IoU
+over the views), ``sil_depth_l1`` (the mean depth difference over the pixels both meshes cover) and
+``sil_views``, and the reduce averages them; a contributing file without them stops the reduce with
+the object's name.  With the default every file is byte for byte what it was.
 """
 import argparse
 import os
@@ -68,6 +79,10 @@ def add_mesh_metric_args(ap):
     ap.add_argument("--min_component_frac", type=float, default=None, metavar="F",
                     help="keep the predicted mesh's components with at least F x the faces of the largest "
                          "(0 < F <= 1; not with --components largest)")
+    ap.add_argument("--sil_views", type=int, default=0, metavar="N",
+                    help="also score the silhouette IoU and depth error from N cameras around the pair (0 = off)")
+    ap.add_argument("--sil_size", type=int, default=128, help="image side of --sil_views, pixels")
+    ap.add_argument("--sil_focal", type=float, default=131.25, help="focal length of --sil_views, pixels")
 
 
 def component_args_error(args):
@@ -78,6 +93,33 @@ def component_args_error(args):
         if not 0.0 < args.min_component_frac <= 1.0:
             return "--min_component_frac must be in (0, 1]"
     return None
+
+
+def sil_args_error(args):
+    """The message for bad silhouette flags, or None."""
+    if args.sil_views < 0:
+        return "--sil_views must be >= 0"
+    if args.sil_views and (args.sil_size < 1 or not args.sil_focal > 0.0):
+        return "--sil_size must be >= 1 and --sil_focal > 0"
+    return None
+
+
+def sil_radius(args):
+    """The camera distance from which a sphere of radius 1.05 at the origin fills the field of view."""
+    import math
+
+    return 1.05 / math.sin(math.atan(0.5 * args.sil_size / args.sil_focal))
+
+
+def silhouette(pred, gt, args, backend):
+    """pnr.evaluate.silhouette_scores of the pair from the --sil_views cameras."""
+    import torch
+
+    from pnr import evaluate
+
+    poses, _ = evaluate.sphere_poses(args.sil_views, sil_radius(args))
+    return evaluate.silhouette_scores(pred, gt, torch.from_numpy(poses).float(), args.sil_size, args.sil_size,
+                                      args.sil_focal, backend=backend)
 
 
 def cleaning(args):
@@ -127,11 +169,12 @@ def prepare_pair(pred_verts, gt_verts, args):
 
 def metric_names(args):
     """The lines of a metrics file, in order: the surface scores, then with --iou the volume scores,
-    then with a cleanup flag the component counts."""
+    then with a cleanup flag the component counts, then with --sil_views the silhouette scores."""
     from pnr import evaluate
 
     return (tuple(evaluate.MESH_METRIC_NAMES) + (tuple(evaluate.VOLUME_METRIC_NAMES) if args.iou else ())
-            + (tuple(evaluate.CLEAN_INFO_NAMES) if cleaning(args) else ()))
+            + (tuple(evaluate.CLEAN_INFO_NAMES) if cleaning(args) else ())
+            + (tuple(evaluate.SIL_METRIC_NAMES) if args.sil_views else ()))
 
 
 def write_metrics(path, scores, names):
@@ -153,6 +196,8 @@ def score_object(pred, gt_path, out_path, args, backend, clean_info=None):
                                           backend=backend))
     if cleaning(args):
         scores.update(clean_info)
+    if args.sil_views:
+        scores.update(silhouette((pv, pred[1]), (gv, gf), args, backend))
     write_metrics(out_path, scores, metric_names(args))
     return scores
 
@@ -221,6 +266,11 @@ def run_reduce(args):
                 raise SystemExit("eval_mesh: %s of object %s has no component counts (scored without --components / "
                                  "--min_component_frac; run the map again with the flag and --overwrite)"
                                  % (OUT_NAME, x))
+    if args.sil_views:
+        for x, row in zip(folders, rows):
+            if any(name not in row for name in evaluate.SIL_METRIC_NAMES):
+                raise SystemExit("eval_mesh: %s of object %s has no silhouette scores (scored without --sil_views; run "
+                                 "the map again with --sil_views and --overwrite)" % (OUT_NAME, x))
     lines = []
     for name in names:
         acc = 0.0
@@ -243,6 +293,8 @@ def main(argv=None):
         raise SystemExit("eval_mesh: --n_iou_points must be >= 1")
     if component_args_error(args):
         raise SystemExit("eval_mesh: " + component_args_error(args))
+    if sil_args_error(args):
+        raise SystemExit("eval_mesh: " + sil_args_error(args))
     if not args.reduce_only:
         print(">>> Compute")
         run_map(args)
