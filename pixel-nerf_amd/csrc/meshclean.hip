@@ -27,7 +27,7 @@
 // (ascending face index), thread j adding positions j, j + B, j + 2 B, ... from 0, the threads
 // folded by a fixed butterfly and the waves in ascending order.  The order is a function of the
 // component's own face sequence: bit-identical from run to run and inside any larger mesh.
-#include "pnr_common.h"
+#include "mesh_dev.h"
 #include "pnr_launch.h"
 
 namespace pnr {
@@ -36,7 +36,6 @@ namespace mck {
 constexpr int kThreads = PNR_MESH_CLEAN_BLOCK;
 constexpr int kSumThreads = 1024, kSumWaves = kSumThreads / kWave;
 constexpr int64_t kMaxVerts = (int64_t)1 << 29;   // the weld table (2 .. 4 V slots) keeps 32-bit slot indices
-constexpr int64_t kMaxCount = 0x7fffffff;
 constexpr int kLaunches = 3;                      // init, hook, flatten
 
 __device__ __forceinline__ uint32_t canon_bits(float x) { return __float_as_uint(x + 0.0f); }   // -0 + 0 = +0
@@ -133,14 +132,13 @@ __global__ __launch_bounds__(kThreads) void k_cc_hook(const int32_t *__restrict_
                                                       int32_t *parent, int32_t *bad) {
     const uint32_t t = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
     if (t >= nt) return;
-    const uint32_t i0 = (uint32_t)faces[3 * (size_t)t], i1 = (uint32_t)faces[3 * (size_t)t + 1],
-                   i2 = (uint32_t)faces[3 * (size_t)t + 2];
-    if (i0 >= nv || i1 >= nv || i2 >= nv) {   // a negative index is a large unsigned one
+    uint32_t i[3];
+    if (!face_indices(faces, t, nv, i)) {
         atomicOr(bad, 1);
         return;
     }
-    if (i0 != i1) unite(parent, (int32_t)i0, (int32_t)i1);
-    if (i1 != i2) unite(parent, (int32_t)i1, (int32_t)i2);
+    if (i[0] != i[1]) unite(parent, (int32_t)i[0], (int32_t)i[1]);
+    if (i[1] != i[2]) unite(parent, (int32_t)i[1], (int32_t)i[2]);
 }
 
 // thread i < nv labels vertex i, thread i < nt face i; `parent` is only read here
@@ -182,10 +180,9 @@ __device__ __forceinline__ void face_terms(const float *__restrict__ verts, uint
     area = 0.0;
     vol = 0.0;
     if (t < 0 || t >= (int64_t)nt) return;
-    const uint32_t i0 = (uint32_t)faces[3 * (size_t)t], i1 = (uint32_t)faces[3 * (size_t)t + 1],
-                   i2 = (uint32_t)faces[3 * (size_t)t + 2];
-    if (i0 >= nv || i1 >= nv || i2 >= nv) return;
-    const float *pa = verts + 3 * (size_t)i0, *pb = verts + 3 * (size_t)i1, *pc = verts + 3 * (size_t)i2;
+    uint32_t i[3];
+    if (!face_indices(faces, (size_t)t, nv, i)) return;
+    const float *pa = verts + 3 * (size_t)i[0], *pb = verts + 3 * (size_t)i[1], *pc = verts + 3 * (size_t)i[2];
     const double ax = pa[0], ay = pa[1], az = pa[2], bx = pb[0], by = pb[1], bz = pb[2], cx = pc[0], cy = pc[1],
                  cz = pc[2];
     const double ux = bx - ax, uy = by - ay, uz = bz - az, wx = cx - ax, wy = cy - ay, wz = cz - az;
@@ -232,8 +229,6 @@ static uint32_t table_capacity(int64_t nv) {
     return cap;
 }
 
-static inline unsigned blocks(uint32_t n) { return (n + kThreads - 1) / kThreads; }
-
 }  // namespace mck
 
 size_t mesh_weld_workspace_bytes(int64_t n_verts) {
@@ -257,11 +252,10 @@ int launch_mesh_weld(const float *verts, int64_t n_verts, void *ws, size_t bytes
     int32_t *table = static_cast<int32_t *>(ws);
     if (hipMemsetAsync(table, 0xff, sizeof(int32_t) * (size_t)cap, st) != hipSuccess)   // every slot -1
         return fail(PNR_ERR_HIP, "pnr_mesh_weld: memset failed");
-    hipLaunchKernelGGL(mck::k_weld_insert, dim3(mck::blocks(nv)), dim3(mck::kThreads), 0, st, verts, nv, table,
-                       cap - 1);
+    const dim3 grid(blocks(nv, mck::kThreads));
+    hipLaunchKernelGGL(mck::k_weld_insert, grid, dim3(mck::kThreads), 0, st, verts, nv, table, cap - 1);
     if (!launch_ok("weld_insert")) return PNR_ERR_HIP;
-    hipLaunchKernelGGL(mck::k_weld_lookup, dim3(mck::blocks(nv)), dim3(mck::kThreads), 0, st, verts, nv, table, cap - 1,
-                       remap);
+    hipLaunchKernelGGL(mck::k_weld_lookup, grid, dim3(mck::kThreads), 0, st, verts, nv, table, cap - 1, remap);
     return launch_ok("weld_lookup") ? PNR_OK : PNR_ERR_HIP;
 }
 
@@ -269,7 +263,7 @@ static int components_check(int64_t n_verts, int64_t n_faces) {
     if (n_verts < 1 || n_faces < 0)
         return fail(PNR_ERR_INVALID, "pnr_mesh_components: n_verts must be >= 1 and n_faces >= 0 (got %lld, %lld)",
                     (long long)n_verts, (long long)n_faces);
-    if (n_verts > mck::kMaxCount || n_faces > mck::kMaxCount)
+    if (n_verts > kMaxCount || n_faces > kMaxCount)
         return fail(PNR_ERR_UNSUPPORTED, "pnr_mesh_components: n_verts or n_faces above 2^31 - 1");
     return PNR_OK;
 }
@@ -291,26 +285,20 @@ int launch_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_vert
     int32_t *parent = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + 256);
     if (hipMemsetAsync(bad, 0, sizeof(int32_t), st) != hipSuccess)
         return fail(PNR_ERR_HIP, "pnr_mesh_components: memset failed");
-    hipLaunchKernelGGL(mck::k_cc_init, dim3(mck::blocks(nv)), dim3(mck::kThreads), 0, st, parent, nv);
+    hipLaunchKernelGGL(mck::k_cc_init, dim3(blocks(nv, mck::kThreads)), dim3(mck::kThreads), 0, st, parent, nv);
     if (!launch_ok("cc_init")) return PNR_ERR_HIP;
     if (nt) {
-        hipLaunchKernelGGL(mck::k_cc_hook, dim3(mck::blocks(nt)), dim3(mck::kThreads), 0, st, faces, nt, nv, parent,
-                           bad);
+        hipLaunchKernelGGL(mck::k_cc_hook, dim3(blocks(nt, mck::kThreads)), dim3(mck::kThreads), 0, st, faces, nt, nv,
+                           parent, bad);
         if (!launch_ok("cc_hook")) return PNR_ERR_HIP;
     }
-    hipLaunchKernelGGL(mck::k_cc_flatten, dim3(mck::blocks(nv > nt ? nv : nt)), dim3(mck::kThreads), 0, st, parent, nv,
-                       faces, nt, vert_label, face_label);
+    hipLaunchKernelGGL(mck::k_cc_flatten, dim3(blocks(nv > nt ? nv : nt, mck::kThreads)), dim3(mck::kThreads), 0, st,
+                       parent, nv, faces, nt, vert_label, face_label);
     if (!launch_ok("cc_flatten")) return PNR_ERR_HIP;
     if (launches) *launches = nt ? mck::kLaunches : mck::kLaunches - 1;
     // the index flag: the one read-back, as pnr_mesh_sample's
     int32_t h_bad = 0;
-    if (hipMemcpyAsync(&h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail(PNR_ERR_HIP, "pnr_mesh_components: reading the index flag failed: %s",
-                    hipGetErrorString(hipGetLastError()));
-    if (h_bad)
-        return fail(PNR_ERR_INVALID, "pnr_mesh_components: a face index lies outside [0, %lld)", (long long)n_verts);
-    return PNR_OK;
+    return read_index_flag(&h_bad, bad, sizeof(h_bad), st, n_verts, "pnr_mesh_components", "index flag");
 }
 
 int launch_mesh_component_sums(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
@@ -318,7 +306,7 @@ int launch_mesh_component_sums(const float *verts, int64_t n_verts, const int32_
                                hipStream_t st) {
     if (n_verts < 1 || n_faces < 1 || n_components < 1)
         return fail(PNR_ERR_INVALID, "pnr_mesh_component_sums: n_verts, n_faces and n_components must be >= 1");
-    if (n_verts > mck::kMaxCount || n_faces > mck::kMaxCount || n_components > mck::kMaxCount)
+    if (n_verts > kMaxCount || n_faces > kMaxCount || n_components > kMaxCount)
         return fail(PNR_ERR_UNSUPPORTED, "pnr_mesh_component_sums: a count above 2^31 - 1");
     hipLaunchKernelGGL(mck::k_component_sums, dim3((uint32_t)n_components), dim3(mck::kSumThreads), 0, st, verts,
                        (uint32_t)n_verts, faces, (uint32_t)n_faces, order, seg_start, out);

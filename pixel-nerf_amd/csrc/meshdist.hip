@@ -26,7 +26,7 @@
 // Reduction: one workgroup per direction, each thread a strided run in ascending order, waves by
 // a fixed butterfly, the wave sums in wave order; fp64 throughout.  A direction's four sums depend
 // on that direction's inputs only.
-#include "pnr_common.h"
+#include "mesh_dev.h"
 #include "pnr_launch.h"
 
 namespace pnr {
@@ -34,7 +34,6 @@ namespace msk {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = PNR_MESH_SCAN_CHUNK, kGroup = kChunk * kChunk;
-constexpr int64_t kMaxCount = 0x7fffffff;   // int32 indices
 static_assert(kChunk == kThreads, "one thread per chunk of a group, one chunk per thread");
 
 // workspace header: the bad-index flag and the total area, read back by the host
@@ -52,11 +51,10 @@ __global__ __launch_bounds__(kThreads) void k_ms_area(const float *__restrict__ 
                                                       double *__restrict__ cdf, Header *__restrict__ hdr) {
     const uint32_t t = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
     if (t >= nt) return;
-    const uint32_t i0 = (uint32_t)faces[3 * (size_t)t], i1 = (uint32_t)faces[3 * (size_t)t + 1],
-                   i2 = (uint32_t)faces[3 * (size_t)t + 2];
+    uint32_t i[3];
     double area = 0.0;
-    if (i0 < nv && i1 < nv && i2 < nv) {   // a negative index is a large unsigned one
-        const float *a = verts + 3 * (size_t)i0, *b = verts + 3 * (size_t)i1, *c = verts + 3 * (size_t)i2;
+    if (face_indices(faces, t, nv, i)) {
+        const float *a = verts + 3 * (size_t)i[0], *b = verts + 3 * (size_t)i[1], *c = verts + 3 * (size_t)i[2];
         const double ax = a[0], ay = a[1], az = a[2];
         const double ux = (double)b[0] - ax, uy = (double)b[1] - ay, uz = (double)b[2] - az;
         const double vx = (double)c[0] - ax, vy = (double)c[1] - ay, vz = (double)c[2] - az;
@@ -285,7 +283,7 @@ struct Plan {
 static int plan(int64_t n, int64_t m, Plan &pl) {
     if (n < 1 || m < 1)
         return fail(PNR_ERR_INVALID, "nearest: n and m must be >= 1 (got %lld, %lld)", (long long)n, (long long)m);
-    if (n > msk::kMaxCount || m > kMaxSlices * kSlice)
+    if (n > kMaxCount || m > kMaxSlices * kSlice)
         return fail(PNR_ERR_UNSUPPORTED, "nearest: n above 2^31 - 1 or m above %lld (got %lld, %lld)",
                     (long long)(kMaxSlices * kSlice), (long long)n, (long long)m);
     pl.n = (uint32_t)n;
@@ -362,7 +360,7 @@ int launch_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces
     if (n < 1 || n_verts < 1)
         return fail(PNR_ERR_INVALID, "pnr_mesh_sample: n and n_verts must be >= 1 (got %lld, %lld)", (long long)n,
                     (long long)n_verts);
-    if (n > msk::kMaxCount || n_verts > msk::kMaxCount)
+    if (n > kMaxCount || n_verts > kMaxCount)
         return fail(PNR_ERR_UNSUPPORTED, "pnr_mesh_sample: n or n_verts above 2^31 - 1");
     if (!ws || bytes < pl.total)
         return fail(PNR_ERR_WORKSPACE, "pnr_mesh_sample: workspace %zu bytes, needs %zu", bytes, pl.total);
@@ -372,9 +370,8 @@ int launch_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces
     double *cdf = reinterpret_cast<double *>(w + pl.off_cdf);
     if (hipMemsetAsync(hdr, 0, sizeof(msk::Header), st) != hipSuccess)
         return fail(PNR_ERR_HIP, "pnr_mesh_sample: memset failed");
-    const unsigned tb = (pl.nt + msk::kThreads - 1) / msk::kThreads;
-    hipLaunchKernelGGL(msk::k_ms_area, dim3(tb), dim3(msk::kThreads), 0, st, verts, (uint32_t)n_verts, faces, pl.nt,
-                       cdf, hdr);
+    hipLaunchKernelGGL(msk::k_ms_area, dim3(blocks(pl.nt, msk::kThreads)), dim3(msk::kThreads), 0, st, verts,
+                       (uint32_t)n_verts, faces, pl.nt, cdf, hdr);
     if (!launch_ok("ms_area")) return PNR_ERR_HIP;
     hipLaunchKernelGGL(msk::k_ms_scan_group, dim3(pl.ng), dim3(msk::kThreads), 0, st, cdf, pl.nt, gtot);
     if (!launch_ok("ms_scan_group")) return PNR_ERR_HIP;
@@ -382,16 +379,12 @@ int launch_mesh_sample(const float *verts, int64_t n_verts, const int32_t *faces
     if (!launch_ok("ms_scan_top")) return PNR_ERR_HIP;
     // the flag and the total before anything is read through a face index: the one read-back
     msk::Header h;
-    if (hipMemcpyAsync(&h, hdr, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail(PNR_ERR_HIP, "pnr_mesh_sample: reading the totals failed: %s", hipGetErrorString(hipGetLastError()));
-    if (h.bad)
-        return fail(PNR_ERR_INVALID, "pnr_mesh_sample: a face index lies outside [0, %lld)", (long long)n_verts);
+    rc = read_index_flag(&h, hdr, sizeof(h), st, n_verts, "pnr_mesh_sample", "totals");
+    if (rc) return rc;
     if (!(h.total > 0.0) || !(h.total < __builtin_inf()))
         return fail(PNR_ERR_INVALID, "pnr_mesh_sample: the total area is %g, nothing to sample", h.total);
-    const unsigned sb = ((uint32_t)n + msk::kThreads - 1) / msk::kThreads;
-    hipLaunchKernelGGL(msk::k_ms_sample, dim3(sb), dim3(msk::kThreads), 0, st, verts, faces, pl.nt, cdf, goff, hdr,
-                       seed, (uint32_t)n, points, normals, tri);
+    hipLaunchKernelGGL(msk::k_ms_sample, dim3(blocks((size_t)n, msk::kThreads)), dim3(msk::kThreads), 0, st, verts,
+                       faces, pl.nt, cdf, goff, hdr, seed, (uint32_t)n, points, normals, tri);
     return launch_ok("ms_sample") ? PNR_OK : PNR_ERR_HIP;
 }
 
@@ -405,7 +398,7 @@ int launch_nearest(const float *a, int64_t n, const float *b, int64_t m, void *w
     nnk::Plan pl;
     int rc = nnk::plan(n, m, pl);
     if (rc) return rc;
-    const dim3 grid((pl.n + nnk::kQ - 1) / nnk::kQ, pl.slices);
+    const dim3 grid(blocks(pl.n, nnk::kQ), pl.slices);
     if (pl.slices == 1) {
         hipLaunchKernelGGL(nnk::k_nearest, grid, dim3(nnk::kThreads), 0, st, a, pl.n, b, pl.m, d2, idx);
         return launch_ok("nearest") ? PNR_OK : PNR_ERR_HIP;
@@ -417,7 +410,7 @@ int launch_nearest(const float *a, int64_t n, const float *b, int64_t m, void *w
     int32_t *p_idx = reinterpret_cast<int32_t *>(w + pl.off_idx);
     hipLaunchKernelGGL(nnk::k_nearest, grid, dim3(nnk::kThreads), 0, st, a, pl.n, b, pl.m, p_d2, p_idx);
     if (!launch_ok("nearest")) return PNR_ERR_HIP;
-    hipLaunchKernelGGL(nnk::k_nearest_combine, dim3((pl.n + nnk::kThreads - 1) / nnk::kThreads), dim3(nnk::kThreads),
+    hipLaunchKernelGGL(nnk::k_nearest_combine, dim3(blocks(pl.n, nnk::kThreads)), dim3(nnk::kThreads),
                        0, st, p_d2, p_idx, pl.n, pl.slices, d2, idx);
     return launch_ok("nearest_combine") ? PNR_OK : PNR_ERR_HIP;
 }
@@ -428,7 +421,7 @@ int launch_mesh_distance_reduce(const float *d2_ab, const int32_t *idx_ab, int64
     if (n < 1 || m < 1)
         return fail(PNR_ERR_INVALID, "pnr_mesh_distance_reduce: n and m must be >= 1 (got %lld, %lld)", (long long)n,
                     (long long)m);
-    if (n > msk::kMaxCount || m > msk::kMaxCount)
+    if (n > kMaxCount || m > kMaxCount)
         return fail(PNR_ERR_UNSUPPORTED, "pnr_mesh_distance_reduce: n or m above 2^31 - 1");
     hipLaunchKernelGGL(mdk::k_md_reduce, dim3(2), dim3(mdk::kThreads), 0, st, d2_ab, idx_ab, (uint32_t)n, d2_ba,
                        idx_ba, (uint32_t)m, normals_a, normals_b, tau, out);

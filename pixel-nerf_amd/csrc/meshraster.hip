@@ -21,7 +21,7 @@
 // stale read is only ever too large).  k_raster_resolve decodes the key and scales the camera-z depth
 // by the length of the pixel's direction; k_raster_shade colours from face and depth.  No float
 // atomics, no LDS, no host sync.
-#include "pnr_common.h"
+#include "mesh_dev.h"
 #include "pnr_launch.h"
 
 namespace pnr {
@@ -29,7 +29,6 @@ namespace rst {
 
 constexpr int kThreads = PNR_RASTER_BLOCK, kTile = PNR_RASTER_TILE, kSmall = PNR_RASTER_SMALL_PIXELS;
 constexpr int kMaxSide = 8192, kMaxLights = PNR_RASTER_MAX_LIGHTS;
-constexpr int64_t kMaxCount = 0x7fffffff;
 constexpr unsigned long long kEmpty = ~0ull;
 static_assert(kTile * kTile == kWave, "one pixel of the block per lane");
 static_assert(kThreads % kWave == 0, "whole waves");
@@ -51,11 +50,6 @@ struct Shading {
     int n_lights;
     float albedo[3], ambient, background[3];
 };
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    const float s = (x - x) + (y - y) + (z - z);
-    return s == s;
-}
 
 __device__ __forceinline__ Cam load_cam(const float *__restrict__ poses, int pose_rows, int64_t view) {
     const float *P = poses + view * pose_rows * 4;
@@ -137,11 +131,9 @@ struct FaceSetup {
 __device__ __forceinline__ bool face_setup(const float *__restrict__ verts, uint32_t nv,
                                            const int32_t *__restrict__ faces, uint32_t t, const Cam &cam,
                                            const View &vw, FaceSetup &fs) {
-    const uint32_t i0 = (uint32_t)faces[3 * (size_t)t], i1 = (uint32_t)faces[3 * (size_t)t + 1],
-                   i2 = (uint32_t)faces[3 * (size_t)t + 2];
-    if (!(i0 < nv && i1 < nv && i2 < nv)) return false;   // a negative index is a large unsigned one
+    uint32_t idx[3];
+    if (!face_indices(faces, t, nv, idx)) return false;
     float w[3][3], c[3][3];
-    const uint32_t idx[3] = {i0, i1, i2};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
 #pragma unroll
@@ -303,11 +295,10 @@ __global__ __launch_bounds__(kThreads) void k_raster_shade(const float *__restri
     float col[3] = {sh.background[0], sh.background[1], sh.background[2]}, nrm[3] = {0.f, 0.f, 0.f};
     const uint32_t t = (uint32_t)face_in[p];
     if (t < n_faces) {   // -1 is a large unsigned one
-        const uint32_t i0 = (uint32_t)faces[3 * (size_t)t], i1 = (uint32_t)faces[3 * (size_t)t + 1],
-                       i2 = (uint32_t)faces[3 * (size_t)t + 2];
-        if (i0 < n_verts && i1 < n_verts && i2 < n_verts) {
+        uint32_t fi[3];
+        if (face_indices(faces, t, n_verts, fi)) {
             const Cam cam = load_cam(poses, pose_rows, (int64_t)view);
-            const float *a = verts + 3 * (size_t)i0, *b = verts + 3 * (size_t)i1, *c = verts + 3 * (size_t)i2;
+            const float *a = verts + 3 * (size_t)fi[0], *b = verts + 3 * (size_t)fi[1], *c = verts + 3 * (size_t)fi[2];
             const float u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, w[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
             float g[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
             const float gl = sqrtf(dot3(g, g));
@@ -361,6 +352,20 @@ static bool finite_view(float fx, float fy, float cx, float cy) {
     return fx - fx == 0.f && fy - fy == 0.f && cx - cx == 0.f && cy - cy == 0.f && fx != 0.f && fy != 0.f;
 }
 
+// what pnr_mesh_raster and pnr_mesh_shade (`fn`) refuse alike: the shape, the vertex count, the camera
+static int check(const char *fn, int64_t nv, int h, int w, int64_t n_faces, int64_t n_verts, float fx, float fy,
+                 float cx, float cy, Plan &pl) {
+    if (!plan(nv, h, w, n_faces, pl))
+        return fail(PNR_ERR_UNSUPPORTED,
+                    "%s: %lld views of %d x %d with %lld faces not supported (sides in 1 .. %d, nv h w and "
+                    "n_faces in 1 .. 2^31 - 1)", fn, (long long)nv, w, h, (long long)n_faces, kMaxSide);
+    if (n_verts < 1 || n_verts > kMaxCount)
+        return fail(PNR_ERR_INVALID, "%s: n_verts must be in 1 .. 2^31 - 1 (got %lld)", fn, (long long)n_verts);
+    if (!finite_view(fx, fy, cx, cy))
+        return fail(PNR_ERR_INVALID, "%s: fx, fy, cx, cy must be finite, fx and fy not 0", fn);
+    return PNR_OK;
+}
+
 }  // namespace rst
 
 size_t mesh_raster_workspace_bytes(int64_t nv, int h, int w, int64_t n_faces) {
@@ -372,24 +377,17 @@ int launch_mesh_raster(const float *verts, int64_t n_verts, const int32_t *faces
                        int64_t nv, int pose_rows, int w, int h, float fx, float fy, float cx, float cy, void *ws,
                        size_t bytes, int32_t *face_out, float *depth_out, int small_max, hipStream_t st) {
     rst::Plan pl;
-    if (!rst::plan(nv, h, w, n_faces, pl))
-        return fail(PNR_ERR_UNSUPPORTED,
-                    "pnr_mesh_raster: %lld views of %d x %d with %lld faces not supported (sides in 1 .. %d, nv h w and "
-                    "n_faces in 1 .. 2^31 - 1)", (long long)nv, w, h, (long long)n_faces, rst::kMaxSide);
-    if (n_verts < 1 || n_verts > rst::kMaxCount)
-        return fail(PNR_ERR_INVALID, "pnr_mesh_raster: n_verts must be in 1 .. 2^31 - 1 (got %lld)",
-                    (long long)n_verts);
-    if (!rst::finite_view(fx, fy, cx, cy))
-        return fail(PNR_ERR_INVALID, "pnr_mesh_raster: fx, fy, cx, cy must be finite, fx and fy not 0");
+    const int rc = rst::check("pnr_mesh_raster", nv, h, w, n_faces, n_verts, fx, fy, cx, cy, pl);
+    if (rc) return rc;
     if (!ws || bytes < pl.total)
         return fail(PNR_ERR_WORKSPACE, "pnr_mesh_raster: workspace %zu bytes, needs %zu", bytes, pl.total);
     if (small_max < 0) small_max = rst::kSmall;
     unsigned long long *keys = static_cast<unsigned long long *>(ws);
     const rst::View vw{w, h, fx, fy, cx, cy};
-    const unsigned pix_blocks = (unsigned)((pl.n_pix + rst::kThreads - 1) / rst::kThreads);
+    const unsigned pix_blocks = blocks(pl.n_pix, rst::kThreads);
     hipLaunchKernelGGL(rst::k_raster_fill, dim3(pix_blocks), dim3(rst::kThreads), 0, st, keys, pl.n_pix);
     if (!launch_ok("raster_fill")) return PNR_ERR_HIP;
-    const dim3 grid((unsigned)((n_faces + rst::kThreads - 1) / rst::kThreads), (unsigned)(nv < 65535 ? nv : 65535));
+    const dim3 grid(blocks((size_t)n_faces, rst::kThreads), (unsigned)(nv < 65535 ? nv : 65535));
     hipLaunchKernelGGL(rst::k_raster_cover, grid, dim3(rst::kThreads), 0, st, verts, (uint32_t)n_verts, faces,
                        (uint32_t)n_faces, poses, pose_rows, (uint32_t)nv, vw, small_max, keys);
     if (!launch_ok("raster_cover")) return PNR_ERR_HIP;
@@ -404,15 +402,8 @@ int launch_mesh_shade(const float *verts, int64_t n_verts, const int32_t *faces,
                       int n_lights, const float albedo[3], float ambient, const float background[3], float *rgb,
                       float *normal, hipStream_t st) {
     rst::Plan pl;
-    if (!rst::plan(nv, h, w, n_faces, pl))
-        return fail(PNR_ERR_UNSUPPORTED,
-                    "pnr_mesh_shade: %lld views of %d x %d with %lld faces not supported (sides in 1 .. %d, nv h w and "
-                    "n_faces in 1 .. 2^31 - 1)", (long long)nv, w, h, (long long)n_faces, rst::kMaxSide);
-    if (n_verts < 1 || n_verts > rst::kMaxCount)
-        return fail(PNR_ERR_INVALID, "pnr_mesh_shade: n_verts must be in 1 .. 2^31 - 1 (got %lld)",
-                    (long long)n_verts);
-    if (!rst::finite_view(fx, fy, cx, cy))
-        return fail(PNR_ERR_INVALID, "pnr_mesh_shade: fx, fy, cx, cy must be finite, fx and fy not 0");
+    const int rc = rst::check("pnr_mesh_shade", nv, h, w, n_faces, n_verts, fx, fy, cx, cy, pl);
+    if (rc) return rc;
     if (n_lights < 0 || n_lights > rst::kMaxLights)
         return fail(PNR_ERR_INVALID, "pnr_mesh_shade: n_lights must be in 0 .. %d (got %d)", rst::kMaxLights, n_lights);
     rst::Shading sh = {};
@@ -424,7 +415,7 @@ int launch_mesh_shade(const float *verts, int64_t n_verts, const int32_t *faces,
     for (int k = 0; k < 3; ++k) sh.albedo[k] = albedo[k], sh.background[k] = background[k];
     sh.ambient = ambient;
     const rst::View vw{w, h, fx, fy, cx, cy};
-    const unsigned pix_blocks = (unsigned)((pl.n_pix + rst::kThreads - 1) / rst::kThreads);
+    const unsigned pix_blocks = blocks(pl.n_pix, rst::kThreads);
     hipLaunchKernelGGL(rst::k_raster_shade, dim3(pix_blocks), dim3(rst::kThreads), 0, st, verts, (uint32_t)n_verts, faces,
                        (uint32_t)n_faces, poses, pose_rows, pl.n_pix, vw, face_in, depth_in, sh, rgb, normal);
     return launch_ok("raster_shade") ? PNR_OK : PNR_ERR_HIP;

@@ -19,7 +19,7 @@
 // angle is +0 (or the query is not finite and its w is NaN anyway).  Each lane adds (double)Omega
 // to its query's fp64 sum in ascending face order; blockIdx.y indexes the slices, and with more
 // than one k_winding_combine folds the per-slice sums in ascending slice order.  No atomics.
-#include "pnr_common.h"
+#include "mesh_dev.h"
 #include "pnr_launch.h"
 
 namespace pnr {
@@ -27,17 +27,10 @@ namespace wnk {
 
 constexpr int kThreads = 256, kQpl = 2;
 constexpr int kQ = PNR_WINDING_QUERIES, kTile = PNR_WINDING_TILE, kSlice = PNR_WINDING_SLICE;
-constexpr int64_t kMaxCount = 0x7fffffff;   // int32 indices
 constexpr int64_t kMaxSlices = 65535;       // gridDim.y
 constexpr double kFourPi = 12.566370614359172;   // 4 pi rounded to fp64
 static_assert(kQ == kThreads * kQpl, "kQpl queries per lane");
 static_assert(kSlice % kTile == 0 && kTile % kThreads == 0 && kTile % 4 == 0, "whole tiles, whole records");
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    // x - x is 0 for a finite x and NaN for +-inf or NaN
-    const float s = (x - x) + (y - y) + (z - z);
-    return s == s;
-}
 
 // The header fixes where the pair arithmetic rounds.  Plain operators under this pragma are never
 // fused; hipcc's __fmul_rn / __fsub_rn are plain operators in ITS header, outside the pragma, where
@@ -99,10 +92,10 @@ __global__ __launch_bounds__(kThreads) void k_winding(const float *__restrict__ 
             const uint32_t j = j0 + t;
             float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             if (j < j_end) {
-                const uint32_t i0 = (uint32_t)faces[3 * (size_t)j], i1 = (uint32_t)faces[3 * (size_t)j + 1],
-                               i2 = (uint32_t)faces[3 * (size_t)j + 2];
-                if (i0 < nv && i1 < nv && i2 < nv) {   // a negative index is a large unsigned one
-                    const float *a = verts + 3 * (size_t)i0, *b = verts + 3 * (size_t)i1, *c = verts + 3 * (size_t)i2;
+                uint32_t fi[3];
+                if (face_indices(faces, j, nv, fi)) {
+                    const float *a = verts + 3 * (size_t)fi[0], *b = verts + 3 * (size_t)fi[1],
+                                *c = verts + 3 * (size_t)fi[2];
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
                         v[k] = a[k];
@@ -195,8 +188,8 @@ int launch_winding(const float *verts, int64_t n_verts, const int32_t *faces, in
     int rc = wnk::plan(n, n_faces, pl);
     if (rc) return rc;
     if (n_verts < 1) return fail(PNR_ERR_INVALID, "pnr_winding: n_verts must be >= 1 (got %lld)", (long long)n_verts);
-    if (n_verts > wnk::kMaxCount) return fail(PNR_ERR_UNSUPPORTED, "pnr_winding: n_verts above 2^31 - 1");
-    const dim3 grid((pl.n + wnk::kQ - 1) / wnk::kQ, pl.slices);
+    if (n_verts > kMaxCount) return fail(PNR_ERR_UNSUPPORTED, "pnr_winding: n_verts above 2^31 - 1");
+    const dim3 grid(blocks(pl.n, wnk::kQ), pl.slices);
     if (pl.slices == 1) {
         hipLaunchKernelGGL(wnk::k_winding, grid, dim3(wnk::kThreads), 0, st, verts, (uint32_t)n_verts, faces, pl.nt,
                            points, pl.n, w, 1);
@@ -208,13 +201,13 @@ int launch_winding(const float *verts, int64_t n_verts, const int32_t *faces, in
     hipLaunchKernelGGL(wnk::k_winding, grid, dim3(wnk::kThreads), 0, st, verts, (uint32_t)n_verts, faces, pl.nt, points,
                        pl.n, part, 0);
     if (!launch_ok("winding")) return PNR_ERR_HIP;
-    hipLaunchKernelGGL(wnk::k_winding_combine, dim3((pl.n + wnk::kThreads - 1) / wnk::kThreads), dim3(wnk::kThreads), 0,
+    hipLaunchKernelGGL(wnk::k_winding_combine, dim3(blocks(pl.n, wnk::kThreads)), dim3(wnk::kThreads), 0,
                        st, part, pl.n, pl.slices, w);
     return launch_ok("winding_combine") ? PNR_OK : PNR_ERR_HIP;
 }
 
 int launch_box_sample(const float lo[3], const float ext[3], int64_t n, uint64_t seed, float *points, hipStream_t st) {
-    hipLaunchKernelGGL(wnk::k_box_sample, dim3(((uint32_t)n + wnk::kThreads - 1) / wnk::kThreads), dim3(wnk::kThreads),
+    hipLaunchKernelGGL(wnk::k_box_sample, dim3(blocks((size_t)n, wnk::kThreads)), dim3(wnk::kThreads),
                        0, st, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], seed, (uint32_t)n, points);
     return launch_ok("box_sample") ? PNR_OK : PNR_ERR_HIP;
 }

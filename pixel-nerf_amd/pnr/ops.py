@@ -182,7 +182,8 @@ NEAREST_SLICE = 4096
 MESH_SCAN_CHUNK = 256
 
 
-def _cloud(t, name, dtype=torch.float32):
+def _typed(t, name, dtype):
+    """``t`` where it is a tensor of ``dtype`` on a HIP device; raises otherwise."""
     if not torch.is_tensor(t):
         raise TypeError("%s must be a tensor" % name)
     if t.device.type != "cuda":
@@ -190,9 +191,49 @@ def _cloud(t, name, dtype=torch.float32):
                          "fallback" % (name, t.device))
     if t.dtype != dtype:
         raise ValueError("pnr: %s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
+    return t
+
+
+def _cloud(t, name, dtype=torch.float32):
+    t = _typed(t, name, dtype)
     if t.dim() != 2 or t.shape[1] != 3:
         raise ValueError("pnr: %s must be (N, 3) (got %s)" % (name, tuple(t.shape)))
     return t.contiguous()
+
+
+def _same_device(**tensors):
+    """Raises unless every named tensor (None: left out) is on the device of the first one."""
+    (ref_name, ref), *rest = tensors.items()
+    for name, t in rest:
+        if t is not None and t.device != ref.device:
+            raise ValueError("pnr: %s is on %s, %s on %s" % (name, t.device, ref_name, ref.device))
+
+
+def _mesh(verts, faces, empty_msg):
+    """The prologue of every wrapper that takes an indexed mesh: ``(verts, faces, V, T)`` from verts
+    (V, 3) float32 and faces (T, 3) int32 on one HIP device, contiguous.  ``empty_msg`` ends the refusal
+    of a mesh without vertices or faces ("... has no surface to sample"); None accepts one."""
+    verts = _cloud(verts, "verts")
+    faces = _cloud(faces, "faces", torch.int32)
+    _same_device(verts=verts, faces=faces)
+    n_v, n_t = int(verts.shape[0]), int(faces.shape[0])
+    if empty_msg is not None and (n_v < 1 or n_t < 1):
+        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) %s" % (n_v, n_t, empty_msg))
+    return verts, faces, n_v, n_t
+
+
+def _seed(seed):
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("pnr: seed must be in 0 .. 2^64 - 1 (got %r)" % (seed,))
+    return int(seed)
+
+
+def _workspace(nbytes, dtype, dev, refusal):
+    """The workspace a ``pnr_*_workspace_bytes`` call sized, as a tensor of ``dtype`` on ``dev``.  A
+    size of 0 is the library's refusal of the shape: PnrError(``refusal``)."""
+    if nbytes == 0:
+        raise _lib.PnrError(refusal)
+    return torch.empty(nbytes // dtype.itemsize, device=dev, dtype=dtype)
 
 
 def mesh_sample(verts, faces, n, seed=0, want_normals=True):
@@ -201,29 +242,22 @@ def mesh_sample(verts, faces, n, seed=0, want_normals=True):
     ``(points (n, 3), normals (n, 3) or None, tri (n,) int32, area)``, area a 0-dim float64 device
     tensor.  Sample s depends on (seed, s) only.  A face index outside [0, V) or a total area of 0
     raises.  One host sync (the library reads its index flag and the total before it samples)."""
-    verts = _cloud(verts, "verts")
-    faces = _cloud(faces, "faces", torch.int32)
-    if faces.device != verts.device:
-        raise ValueError("pnr: faces is on %s, verts on %s" % (faces.device, verts.device))
-    n, n_v, n_t = int(n), int(verts.shape[0]), int(faces.shape[0])
+    verts, faces, n_v, n_t = _mesh(verts, faces, "has no surface to sample")
+    n = int(n)
     if n < 1:
         raise ValueError("pnr: n must be >= 1 (got %d)" % n)
-    if n_v < 1 or n_t < 1:
-        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) has no surface to sample" % (n_v, n_t))
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError("pnr: seed must be in 0 .. 2^64 - 1 (got %r)" % (seed,))
+    seed = _seed(seed)
     lib = _lib.load()
     dev = verts.device
-    nbytes = lib.pnr_mesh_sample_workspace_bytes(n_t)
-    if nbytes == 0 or n >= 2 ** 31:
-        raise _lib.PnrError("pnr_mesh_sample: %d faces / %d samples not supported (below 2^31)" % (n_t, n))
-    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    nbytes = lib.pnr_mesh_sample_workspace_bytes(n_t) if n < 2 ** 31 else 0
+    ws = _workspace(nbytes, torch.float64, dev,
+                    "pnr_mesh_sample: %d faces / %d samples not supported (below 2^31)" % (n_t, n))
     points = torch.empty(n, 3, device=dev, dtype=torch.float32)
     normals = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_normals else None
     tri = torch.empty(n, device=dev, dtype=torch.int32)
     area = torch.empty((), device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_sample(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, n, int(seed), _lib.ptr(ws), nbytes,
+        _lib.check(lib.pnr_mesh_sample(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, n, seed, _lib.ptr(ws), nbytes,
                                        _lib.ptr(points), _lib.ptr(normals), _lib.ptr(tri), _lib.ptr(area),
                                        _lib.stream_of(dev)), "pnr_mesh_sample")
     return points, normals, tri, area
@@ -235,18 +269,15 @@ def nearest(a, b):
     from the coordinate differences; equal distances resolve to the lowest index.  No host sync."""
     a = _cloud(a, "a")
     b = _cloud(b, "b")
-    if b.device != a.device:
-        raise ValueError("pnr: b is on %s, a on %s" % (b.device, a.device))
+    _same_device(a=a, b=b)
     n, m = int(a.shape[0]), int(b.shape[0])
     if n < 1 or m < 1:
         raise ValueError("pnr: a and b must hold at least one point each (got %d, %d)" % (n, m))
     lib = _lib.load()
     dev = a.device
     nbytes = lib.pnr_nearest_workspace_bytes(n, m)
-    if nbytes == 0:
-        raise _lib.PnrError("pnr_nearest_workspace_bytes: %d x %d points not supported (n < 2^31, m <= 65535 * %d)"
-                            % (n, m, NEAREST_SLICE))
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    ws = _workspace(nbytes, torch.float32, dev, "pnr_nearest_workspace_bytes: %d x %d points not supported (n < 2^31, "
+                    "m <= 65535 * %d)" % (n, m, NEAREST_SLICE))
     d2 = torch.empty(n, device=dev, dtype=torch.float32)
     idx = torch.empty(n, device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
@@ -290,9 +321,7 @@ def mesh_distance(pa, na, pb, nb, tau):
         if tuple(na.shape) != tuple(pa.shape) or tuple(nb.shape) != tuple(pb.shape):
             raise ValueError("pnr: normals must match their points (got %s for %s, %s for %s)" % (
                 tuple(na.shape), tuple(pa.shape), tuple(nb.shape), tuple(pb.shape)))
-    for t, name in ((pb, "pb"), (na, "na"), (nb, "nb")):
-        if t is not None and t.device != pa.device:
-            raise ValueError("pnr: %s is on %s, pa on %s" % (name, t.device, pa.device))
+    _same_device(pa=pa, pb=pb, na=na, nb=nb)
     if not float(tau) >= 0.0:
         raise ValueError("pnr: tau must be >= 0 (got %r)" % (tau,))
     n, m = int(pa.shape[0]), int(pb.shape[0])
@@ -330,24 +359,17 @@ def winding_number(verts, faces, points):
     The pairs are scored in fp32 and summed in fp64 in a fixed order: ``w[i]`` depends on
     ``points[i]`` and the mesh only.  A face with an index outside [0, V) contributes 0; a
     non-finite query gives NaN.  No host sync."""
-    verts = _cloud(verts, "verts")
-    faces = _cloud(faces, "faces", torch.int32)
+    verts, faces, n_v, n_t = _mesh(verts, faces, "contains nothing")
     points = _cloud(points, "points")
-    for t, name in ((faces, "faces"), (points, "points")):
-        if t.device != verts.device:
-            raise ValueError("pnr: %s is on %s, verts on %s" % (name, t.device, verts.device))
-    n, n_v, n_t = int(points.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    _same_device(verts=verts, points=points)
+    n = int(points.shape[0])
     if n < 1:
         raise ValueError("pnr: points must hold at least one point (got %d)" % n)
-    if n_v < 1 or n_t < 1:
-        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) contains nothing" % (n_v, n_t))
     lib = _lib.load()
     dev = verts.device
-    nbytes = lib.pnr_winding_workspace_bytes(n, n_t)
-    if nbytes == 0 or n_v >= 2 ** 31:
-        raise _lib.PnrError("pnr_winding_workspace_bytes: %d points x %d faces not supported (n < 2^31, faces <= "
-                            "min(2^31 - 1, 65535 * %d))" % (n, n_t, WINDING_SLICE))
-    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    nbytes = lib.pnr_winding_workspace_bytes(n, n_t) if n_v < 2 ** 31 else 0
+    ws = _workspace(nbytes, torch.float64, dev, "pnr_winding_workspace_bytes: %d points x %d faces not supported "
+                    "(n < 2^31, faces <= min(2^31 - 1, 65535 * %d))" % (n, n_t, WINDING_SLICE))
     w = torch.empty(n, device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
         _lib.check(lib.pnr_winding(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(points), n, _lib.ptr(ws), nbytes,
@@ -373,8 +395,7 @@ def box_sample(lo, hi, n, seed=0, device="cuda"):
     n = int(n)
     if n < 1:
         raise ValueError("pnr: n must be >= 1 (got %d)" % n)
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError("pnr: seed must be in 0 .. 2^64 - 1 (got %r)" % (seed,))
+    seed = _seed(seed)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("pnr: box_sample draws on a HIP device (got %s); the HIP path has no CPU fallback" % (dev,))
@@ -385,7 +406,7 @@ def box_sample(lo, hi, n, seed=0, device="cuda"):
     lib = _lib.load()
     with torch.cuda.device(dev):
         _lib.check(lib.pnr_box_sample(ctypes.cast(c_lo, ctypes.c_void_p), ctypes.cast(c_hi, ctypes.c_void_p), n,
-                                      int(seed), _lib.ptr(points), _lib.stream_of(dev)), "pnr_box_sample")
+                                      seed, _lib.ptr(points), _lib.stream_of(dev)), "pnr_box_sample")
     return points
 
 
@@ -399,33 +420,28 @@ RASTER_MAX_LIGHTS = 8
 
 
 def _raster_args(verts, faces, poses, width, height, focal, c):
+    """What mesh_raster and mesh_shade check and refuse alike; the last entry is the size of
+    mesh_raster's workspace."""
     from . import util
 
-    verts = _cloud(verts, "verts")
-    faces = _cloud(faces, "faces", torch.int32)
-    if not torch.is_tensor(poses):
-        raise TypeError("poses must be a tensor")
-    if poses.device.type != "cuda":
-        raise ValueError("pnr: poses must be on a HIP device (got %s); the HIP path has no CPU "
-                         "fallback" % (poses.device,))
-    if poses.dtype != torch.float32:
-        raise ValueError("pnr: poses must be float32 (got %s)" % (poses.dtype,))
+    verts, faces, n_v, n_t = _mesh(verts, faces, "renders nothing")
+    poses = _typed(poses, "poses", torch.float32)
     if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
         raise ValueError("pnr: poses must be (NV, 4, 4) or (NV, 3, 4) (got %s)" % (tuple(poses.shape),))
     poses = poses.contiguous()
-    for t, name in ((faces, "faces"), (poses, "poses")):
-        if t.device != verts.device:
-            raise ValueError("pnr: %s is on %s, verts on %s" % (name, t.device, verts.device))
-    nv, n_v, n_t = int(poses.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    _same_device(verts=verts, poses=poses)
+    nv = int(poses.shape[0])
     if nv < 1:
         raise ValueError("pnr: poses must hold at least one view (got %d)" % nv)
-    if n_v < 1 or n_t < 1:
-        raise ValueError("pnr: an empty mesh (%d vertices, %d faces) renders nothing" % (n_v, n_t))
     width, height = int(width), int(height)
     if width < 1 or height < 1:
         raise ValueError("pnr: width and height must be >= 1 (got %d, %d)" % (width, height))
     fx, fy, cx, cy = util._focal_c(width, height, focal, c)
-    return verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy
+    nbytes = _lib.load().pnr_mesh_raster_workspace_bytes(nv, height, width, n_t)
+    if nbytes == 0 or n_v >= 2 ** 31:
+        raise _lib.PnrError("pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
+                            "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
+    return verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, nbytes
 
 
 def mesh_raster(verts, faces, poses, width, height, focal, c=None):
@@ -436,14 +452,10 @@ def mesh_raster(verts, faces, poses, width, height, focal, c=None):
     ``util.gen_rays(poses, width, height, focal, ., ., c)``; ``face`` is -1 and ``depth`` 0 where the
     ray hits nothing, else ``depth`` is the distance along the unit direction (the composite's
     depth).  Both are functions of the inputs alone, bit for bit.  No host sync."""
-    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy = _raster_args(verts, faces, poses, width, height,
-                                                                                    focal, c)
+    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, nbytes = _raster_args(
+        verts, faces, poses, width, height, focal, c)
     lib = _lib.load()
     dev = verts.device
-    nbytes = lib.pnr_mesh_raster_workspace_bytes(nv, height, width, n_t)
-    if nbytes == 0 or n_v >= 2 ** 31:
-        raise _lib.PnrError("pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
-                            "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
     ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
     face = torch.empty(nv, height, width, device=dev, dtype=torch.int32)
     depth = torch.empty(nv, height, width, device=dev, dtype=torch.float32)
@@ -480,18 +492,13 @@ def mesh_shade(verts, faces, poses, width, height, focal, face, depth, c=None, l
     ``albedo`` and ``background`` triples; colours of covered pixels are clamped to [0, 254/255]."""
     import ctypes
 
-    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy = _raster_args(verts, faces, poses, width, height,
-                                                                                    focal, c)
+    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, _ = _raster_args(
+        verts, faces, poses, width, height, focal, c)
     dev = verts.device
     for t, name, dtype in ((face, "face", torch.int32), (depth, "depth", torch.float32)):
-        if not torch.is_tensor(t):
-            raise TypeError("%s must be a tensor" % name)
-        if t.device != dev:
-            raise ValueError("pnr: %s is on %s, verts on %s" % (name, t.device, dev))
-        if t.dtype != dtype:
-            raise ValueError("pnr: %s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
-        if tuple(t.shape) != (nv, height, width):
+        if tuple(_typed(t, name, dtype).shape) != (nv, height, width):
             raise ValueError("pnr: %s must be %s (got %s)" % (name, (nv, height, width), tuple(t.shape)))
+    _same_device(verts=verts, face=face, depth=depth)
     lights = [[float(x) for x in l] for l in lights]
     weights = [float(x) for x in weights]
     if len(lights) != len(weights) or len(lights) > RASTER_MAX_LIGHTS or any(len(l) != 3 for l in lights):
@@ -501,9 +508,6 @@ def mesh_shade(verts, faces, poses, width, height, focal, face, depth, c=None, l
     if len(albedo) != 3 or len(background) != 3:
         raise ValueError("pnr: albedo and background must be triples")
     lib = _lib.load()
-    if lib.pnr_mesh_raster_workspace_bytes(nv, height, width, n_t) == 0 or n_v >= 2 ** 31:
-        raise _lib.PnrError("pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
-                            "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
     n_l = len(lights)
     c_l = (ctypes.c_float * max(1, 3 * n_l))(*[x for l in lights for x in l])
     c_w = (ctypes.c_float * max(1, n_l))(*weights)
@@ -536,9 +540,8 @@ def mesh_weld_remap(verts):
         return torch.empty(0, device=dev, dtype=torch.int32)
     lib = _lib.load()
     nbytes = lib.pnr_mesh_weld_workspace_bytes(n_v)
-    if nbytes == 0:
-        raise _lib.PnrError("pnr_mesh_weld_workspace_bytes: %d vertices not supported (1 .. 2^29)" % n_v)
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    ws = _workspace(nbytes, torch.int32, dev,
+                    "pnr_mesh_weld_workspace_bytes: %d vertices not supported (1 .. 2^29)" % n_v)
     remap = torch.empty(n_v, device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
         _lib.check(lib.pnr_mesh_weld(_lib.ptr(verts), n_v, _lib.ptr(ws), nbytes, _lib.ptr(remap), _lib.stream_of(dev)),
@@ -552,12 +555,8 @@ def mesh_weld(verts, faces):
     ``mesh_weld_remap``'s, in ORIGINAL indices; verts' are the vertices with remap[i] == i in ascending
     original order and faces' the same T rows re-indexed into them: no face is dropped, degenerate
     ones included, so row t still is record t of the STL.  One host sync (V' sizes the output)."""
-    verts = _cloud(verts, "verts")
-    faces = _cloud(faces, "faces", torch.int32)
-    if faces.device != verts.device:
-        raise ValueError("pnr: faces is on %s, verts on %s" % (faces.device, verts.device))
+    verts, faces, n_v, _ = _mesh(verts, faces, None)   # an empty mesh welds to itself
     remap = mesh_weld_remap(verts)
-    n_v = int(verts.shape[0])
     keep = remap == torch.arange(n_v, device=verts.device, dtype=torch.int32)
     new_index = torch.cumsum(keep, 0, dtype=torch.int64) - 1
     if faces.numel() and n_v:
@@ -593,10 +592,8 @@ def mesh_components(verts_or_n, faces, return_launches=False):
 
     lib = _lib.load()
     nbytes = lib.pnr_mesh_components_workspace_bytes(n_v, n_t)
-    if nbytes == 0:
-        raise _lib.PnrError("pnr_mesh_components_workspace_bytes: %d vertices / %d faces not supported (below 2^31)"
-                            % (n_v, n_t))
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    ws = _workspace(nbytes, torch.int32, dev, "pnr_mesh_components_workspace_bytes: %d vertices / %d faces not "
+                    "supported (below 2^31)" % (n_v, n_t))
     vert_label = torch.empty(n_v, device=dev, dtype=torch.int32)
     face_label = torch.empty(n_t, device=dev, dtype=torch.int32)
     launches = ctypes.c_int32(0)
@@ -618,15 +615,11 @@ def mesh_component_stats(verts, faces, vert_label, face_label):
     that depends on the component's own faces only, so a component's sums are bit-identical from run
     to run and inside any larger mesh).  The faces are grouped by component with a stable sort; the
     counts are integer bincounts.  One host sync (C)."""
-    verts = _cloud(verts, "verts")
-    faces = _cloud(faces, "faces", torch.int32)
+    verts, faces, n_v, n_t = _mesh(verts, faces, None)   # no faces: every component's sums are 0
     dev = verts.device
-    n_v, n_t = int(verts.shape[0]), int(faces.shape[0])
     for t, name, n in ((vert_label, "vert_label", n_v), (face_label, "face_label", n_t)):
         if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != dev:
             raise ValueError("pnr: %s must be an int32 tensor of shape (%d,) on %s" % (name, n, dev))
-    if faces.device != dev:
-        raise ValueError("pnr: faces is on %s, verts on %s" % (faces.device, dev))
     labels = torch.unique(vert_label)   # sorted ascending
     n_c = int(labels.shape[0])
     vert_id = torch.searchsorted(labels, vert_label)

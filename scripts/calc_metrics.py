@@ -103,14 +103,11 @@ def run_map(args):
     from pnr.data import _imread
 
     list_name, img_dir_name = dataset_layout(args)
-    backend = args.metrics_backend
-    if backend != "numpy":
+    backend = evaluate._resolve_backend(args.metrics_backend, "metrics")
+    if backend == "hip":
         import torch
 
-        if backend == "auto":
-            backend = "hip" if torch.cuda.is_available() else "numpy"
-        if backend == "hip":
-            torch.cuda.set_device(args.gpu_id)
+        torch.cuda.set_device(args.gpu_id)
     print("Scoring with the", backend, "backend")
 
     if args.multicat:

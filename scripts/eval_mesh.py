@@ -203,14 +203,13 @@ def score_object(pred, gt_path, out_path, args, backend, clean_info=None):
 
 
 def resolve_backend(args):
-    backend = args.metrics_backend
-    if backend != "numpy":
+    from pnr import evaluate
+
+    backend = evaluate._resolve_backend(args.metrics_backend, "metrics")
+    if backend == "hip":
         import torch
 
-        if backend == "auto":
-            backend = "hip" if torch.cuda.is_available() else "numpy"
-        if backend == "hip":
-            torch.cuda.set_device(args.gpu_id)
+        torch.cuda.set_device(args.gpu_id)
     return backend
 
 

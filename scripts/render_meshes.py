@@ -130,14 +130,11 @@ def main(argv=None):
 
     from pnr import evaluate, mesh
 
-    backend = args.backend
-    if backend != "numpy":
+    backend = evaluate._resolve_backend(args.backend, "render")
+    if backend == "hip":
         import torch
 
-        if backend == "auto":
-            backend = "hip" if torch.cuda.is_available() else "numpy"
-        if backend == "hip":
-            torch.cuda.set_device(args.gpu_id)
+        torch.cuda.set_device(args.gpu_id)
     print("Rendering with the", backend, "backend")
     prefix = args.prefix or osp.basename(osp.normpath(args.datadir))
     poses, file_poses = evaluate.sphere_poses(args.views, args.cam_radius)

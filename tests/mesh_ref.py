@@ -1,6 +1,8 @@
 """Yardstick of the mesh-metric tests (a helper, not a conftest): the numpy fp64 restatement of
 pnr_mesh_sample's rule (include/pnr_abi.h, "Mesh metrics") built on oracle/philox.py, a brute-force
 fp64 nearest neighbour, the score formulas of Occupancy Networks' eval_pointcloud, and meshes."""
+import subprocess
+
 import numpy as np
 
 from oracle import philox
@@ -138,6 +140,21 @@ def write_eval_tree(root, res, objects):
             v, f = icosphere(3, r_gt)
             mesh.write_stl(os.path.join(gt, name + ".stl"), v + np.float32(0.25), f)   # off-centre: normalised away
     return out, gt
+
+
+# for the eval_mesh.py tests: run the script, read a metrics file as rows of words or as {name: value}
+def _run(cmd):
+    return subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+
+
+def _lines(path):
+    with open(path) as fh:
+        return [ln.split() for ln in fh.read().split("\n")[:-1]]
+
+
+def _read(path):
+    with open(path) as fh:
+        return {k: float(x) for k, x in (ln.split() for ln in fh)}
 
 
 def sphere_slack(subdivisions, radius, n_samples):

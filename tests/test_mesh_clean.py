@@ -5,7 +5,6 @@ and scripts/eval_mesh.py --components / --min_component_frac.  The device kernel
 tests/test_gpu_mesh_clean.py's."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 
 import meshclean_ref as ref
 import mesh_ref
+from mesh_ref import _lines, _run
 from pnr import _lib, evaluate, mesh, ops
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -220,15 +220,6 @@ def test_empty_and_faceless_meshes():
 
 
 # ---- scripts/eval_mesh.py ----------------------------------------------------------------------------
-def _run(cmd):
-    return subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-
-
-def _lines(path):
-    with open(path) as fh:
-        return [ln.split() for ln in fh.read().split("\n")[:-1]]
-
-
 def test_eval_mesh_script_components(tmp_path):
     """Two objects, the prediction of "b" with a far floater (index units).  Default flags: the files of
     the parent's code path (the surface lines only, "b" ruined).  --components largest: the three

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import mesh_ref
+from mesh_ref import _read
 from oracle import philox
 from pnr import _lib, evaluate, mesh
 
@@ -61,7 +62,8 @@ def test_python_constants_are_the_headers():
 
 def test_host_draws_are_the_oracle_stream():
     for seed in (0, 7, 2 ** 40 + 3):
-        assert np.array_equal(evaluate._mesh_draws(seed, 1001), philox.stream(seed, 0, mesh_ref.RNG_MESH, 1001, 3))
+        assert np.array_equal(evaluate._draws(seed, evaluate._RNG_MESH, 1001),
+                              philox.stream(seed, 0, mesh_ref.RNG_MESH, 1001, 3))
 
 
 def test_host_sampling_is_the_restatement():
@@ -139,11 +141,6 @@ def test_normalize_bounds_on_a_known_box():
     t = mesh.normalize_bounds(torch.from_numpy(box), 2.0)
     assert torch.is_tensor(t) and np.allclose(t.numpy(), want, atol=1e-6)
     assert mesh.normalize_bounds(box[:0]).shape == (0, 3)
-
-
-def _read(path):
-    with open(path) as fh:
-        return {k: float(x) for k, x in (ln.split() for ln in fh)}
 
 
 def test_eval_mesh_script_numpy_backend(tmp_path):

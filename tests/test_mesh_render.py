@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import mesh_ref
+from mesh_ref import _lines
 import raster_ref as R
 from pnr import _lib, evaluate, mesh, ops
 from pnr.data import SRNDataset
@@ -220,11 +221,6 @@ def test_render_meshes_script_numpy_backend(tmp_path):
     assert run.returncode == 0 and open(png, "rb").read() == before
     depth = np.load(os.path.join(str(out), "pollen_train", "ball", "depth", "000003.npy"))
     assert depth.shape == (16, 16) and depth.dtype == np.float32 and 0.3 < (depth > 0).mean() < 0.9
-
-
-def _lines(path):
-    with open(path) as fh:
-        return [ln.split() for ln in fh.read().split("\n")[:-1]]
 
 
 def test_eval_mesh_script_silhouette_flags(tmp_path):

@@ -13,6 +13,7 @@ import pytest
 
 import mc_ref
 import mesh_ref
+from mesh_ref import _lines
 import winding_ref
 from oracle import philox
 from pnr import _lib, evaluate, ops
@@ -61,7 +62,8 @@ def test_python_constants_are_the_headers():
 
 def test_host_draws_are_the_oracle_stream():
     for seed in (0, 7, 2 ** 40 + 3):
-        assert np.array_equal(evaluate._volume_draws(seed, 1001), philox.stream(seed, 0, 5, 1001, 3))
+        assert np.array_equal(evaluate._draws(seed, evaluate._RNG_VOLUME, 1001),
+                              philox.stream(seed, 0, 5, 1001, 3))
 
 
 def test_host_box_samples_lie_in_the_box():
@@ -154,11 +156,6 @@ def test_empty_prediction_is_a_result():
         evaluate.volume_iou(gt, empty, n_points=500, backend="numpy")
     with pytest.raises(ValueError):
         evaluate.volume_iou(gt, gt, n_points=500, backend="cuda")
-
-
-def _lines(path):
-    with open(path) as fh:
-        return [ln.split() for ln in fh.read().split("\n")[:-1]]
 
 
 def test_eval_mesh_script_iou_numpy_backend(tmp_path):

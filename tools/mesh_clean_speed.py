@@ -32,24 +32,8 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from mesh_metrics_speed import _stats, events, shader_clock_mhz  # noqa: E402
 from pnr import _lib, evaluate, ops  # noqa: E402
-
-
-def floater_grid(res, dev, n_floaters, seed=0):
-    """Two blobs (signed distance to two spheres, world units over [-1, 1]^3) and n_floaters single
-    voxels set above the level, each at least 0.1 away from the blobs."""
-    g = torch.linspace(-1, 1, res, device=dev)
-    x, y, z = torch.meshgrid(g, g, g, indexing="ij")
-    a = 0.45 - torch.sqrt((x + 0.3) ** 2 + y ** 2 + z ** 2)
-    b = 0.25 - torch.sqrt((x - 0.5) ** 2 + (y - 0.3) ** 2 + z ** 2)
-    grid = torch.maximum(a, b).contiguous()
-    gen = torch.Generator().manual_seed(seed)
-    p = torch.randint(2, res - 2, (4 * n_floaters, 3), generator=gen).to(dev)
-    far = grid[p[:, 0], p[:, 1], p[:, 2]] < -0.1
-    p = p[far][:n_floaters]
-    grid[p[:, 0], p[:, 1], p[:, 2]] = 0.5
-    return grid
+from speed_common import _stats, events, floater_grid, shader_clock_mhz  # noqa: E402
 
 
 def torch_labels(n_verts, faces):

@@ -22,7 +22,6 @@ difference-form brute force.
   python tools/mesh_metrics_speed.py [--out profiles/meshdist/meshdist_speed.json]
 """
 import argparse
-import glob
 import json
 import os
 import statistics
@@ -36,43 +35,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from pnr import evaluate, ops  # noqa: E402
-
-
-def _stats(ms):
-    return dict(median=statistics.median(ms), min=min(ms), max=max(ms), runs=len(ms))
-
-
-def shader_clock_mhz():
-    """The active level of every card's pp_dpm_sclk table (read only), or None."""
-    out = []
-    for path in sorted(glob.glob("/sys/class/drm/card*/device/pp_dpm_sclk")):
-        try:
-            with open(path) as f:
-                out += [int(ln.split()[1].lower().replace("mhz", "")) for ln in f if ln.strip().endswith("*")]
-        except (OSError, ValueError, IndexError):
-            pass
-    return out or None
-
-
-def blob_grid(res, dev, bump):
-    """A 256^3 density: a sphere of radius 0.6 with a low-frequency bump of the given amplitude."""
-    g = torch.linspace(-1, 1, res, device=dev)
-    x, y, z = torch.meshgrid(g, g, g, indexing="ij")
-    r = torch.sqrt(x * x + y * y + z * z)
-    return (0.6 + bump * torch.sin(5 * x) * torch.cos(4 * y) * torch.sin(3 * z) - r).contiguous()
-
-
-def events(fn, warmup, reps):
-    ms = []
-    for i in range(warmup + reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        if i >= warmup:
-            ms.append(a.elapsed_time(b))
-    return ms
+from speed_common import _stats, blob_grid, events, shader_clock_mhz  # noqa: E402
 
 
 def cdist_nearest(a, b, rows):

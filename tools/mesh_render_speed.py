@@ -34,9 +34,8 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from mesh_clean_speed import floater_grid  # noqa: E402
-from mesh_metrics_speed import _stats, events, shader_clock_mhz  # noqa: E402
 from pnr import evaluate, mesh, ops  # noqa: E402
+from speed_common import _stats, events, floater_grid, shader_clock_mhz  # noqa: E402
 
 LIGHTS = dict(lights=[(1.3, 1.3, 1.3), (-1.3, -1.3, 1.3), (0.0, -1.3, 1.3)], weights=[0.55, 0.18, 0.11], ambient=0.15)
 

@@ -28,21 +28,13 @@ import torch  # noqa: E402
 
 from pnr import _lib, ops, synth  # noqa: E402
 from pnr.models import PixelNeRFNet  # noqa: E402
+from speed_common import events  # noqa: E402
 
 HBM_SPEC, HBM_COPY = 8.0e12, 6.29e12   # bytes/s: spec peak; measured float4 copy
 
 
 def _events(fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
+    ms = events(fn, warmup, reps)
     return statistics.median(ms), min(ms), max(ms)
 
 

@@ -34,8 +34,8 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from mesh_metrics_speed import _stats, blob_grid, events, shader_clock_mhz  # noqa: E402
 from pnr import evaluate, ops  # noqa: E402
+from speed_common import _stats, blob_grid, events, shader_clock_mhz  # noqa: E402
 
 SIMDS, CLOCK_HZ, CYCLES_PER_VALU = 256 * 4, 2.4e9, 2   # MI355X: 256 CUs x 4 SIMDs, 2.4 GHz peak
 
