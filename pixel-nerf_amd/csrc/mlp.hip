@@ -64,7 +64,8 @@ struct Args {
     int ns, hl, wl;
     float img_w, img_h;
     float *out;
-    float *xsum;       // scratch: gridDim.x x 2 x (COLS * H) floats (x park, multi-view sum)
+    float *xsum;       // scratch: gridDim.x x 2 x (COLS * H) floats; of a workgroup's pair of regions the
+                       // first is unused, the second holds the multi-view sum
     int64_t n_tiles;
     // training forward (NS == 1): activations for the backward, fp32 row-major [point][width]:
     //   features (64) | z (512) | relu(x) into fc_0 of block b (512 each) |
@@ -156,6 +157,22 @@ typedef const __attribute__((address_space(4))) float *CFloatPtr;
 typedef const __attribute__((address_space(4))) int *CIntPtr;
 __device__ __forceinline__ CFloatPtr as_const(const float *p) { return (CFloatPtr)(uint64_t)p; }
 __device__ __forceinline__ CIntPtr as_const(const int *p) { return (CIntPtr)(uint64_t)p; }
+
+// Multi-view mean (combine_interleaved, util.py:461-471: sum over views, then / ns; ns > 1): view
+// v's x joins the running sum in this thread's slots of xs (v = 0 starts it); after the last
+// view x = sum / ns.
+__device__ __forceinline__ void view_mean(Acc &x, float *xs, int v, int ns) {
+    const float nsf = (float)ns;
+#pragma unroll
+    for (int r = 0; r < RTW; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            f4 *ptr = reinterpret_cast<f4 *>(xs + (r * CT + c) * 256);
+            const f4 sum = v == 0 ? x[r][c] : *ptr + x[r][c];
+            if (v < ns - 1) *ptr = sum;
+            else x[r][c] = sum / nsf;
+        }
+}
 
 // PZ: lin_z from the projected latent (gather_proj) instead of the latent gather + GEMM;
 // MARCH: the fused ray march (a.m), a separate instantiation so that the plain point model
@@ -379,10 +396,35 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
         auto PJ_ = [&]() -> const float * { return pass_f ? march_cfg(a)->proj_f : a.proj; };
         const float *bias = PK() + L.off_bias;
         gc.hdr = PK();
-        // per-workgroup scratch (L2-resident): [0] x parked during fc_0, [1] multi-view sum
-        // (addresses formed at use: nothing per tile stays live across the GEMMs)
-        auto xp_ptr = [&]() { return a.xsum + (int64_t)blockIdx.x * (2 * COLS * H) + wave * (RTW * CT * 256) + opaque_lane(lane) * 4; };
-        auto xs_ptr = [&]() { return xp_ptr() + COLS * H; };
+        // the multi-view sum's slots of this thread: the second of the workgroup's pair of 128 KB
+        // regions of a.xsum, L2-resident (the first is unused; the address is formed at use: nothing
+        // per tile stays live across the GEMMs)
+        auto xs_ptr = [&]() {
+            return a.xsum + (int64_t)blockIdx.x * (2 * COLS * H) + COLS * H + wave * (RTW * CT * 256) + opaque_lane(lane) * 4;
+        };
+        auto W512 = [&](int layer) -> const float * { return PK() + L.off_l512 + (int64_t)layer * L.layer_floats; };
+        // ---- one 512 -> 512 layer: publish relu(src) as the input image, then dst (+)= W relu(src) + b.
+        // fp16 modes prime the layer's weight ring, and every mode loads its bias rows, before the
+        // publish.  The pre_publish_sync that frees the image is the caller's.
+        auto relu_layer = [&](const Acc &src, Acc &dst, int layer, int save_idx, int64_t row0, bool accumulate)
+                              __attribute__((always_inline)) {
+            HRing<KD, NP> R;
+            if constexpr (HP) hring_prime(R, W512(layer) + opaque_lane((int)gc.ws_off));
+            f4 nb[RTW];
+            load_bias(nb, bias + (1 + layer) * H, wave, lane);
+            publish_relu(src, tile, save_idx, row0);
+            lds_barrier();
+            PT(gc, 16);
+            set_bias(dst, nb, accumulate);
+            layer_gemm<PREC, NKB, KD, HP>(dst, W512(layer), gc, 1 + layer, HP ? &R : nullptr);
+        };
+        // ---- residual block blk (resnetfc.py:69-84) on the packed layers l0 (fc_0) and l0 + 1 (fc_1):
+        // h = fc_0(relu(x)); x += fc_1(relu(h)).  row0: the view's first row of the activation save.
+        auto res_block = [&](int blk, int l0, int64_t row0) __attribute__((always_inline)) {
+            relu_layer(x, h, l0, blk, row0, false);
+            pre_publish_sync();
+            relu_layer(h, x, l0 + 1, L.n_blocks + blk, row0, true);
+        };
 
         // source views (LEAN: one, so no view loop; else read at use like every launch constant)
         auto NS = [&]() -> int {
@@ -612,133 +654,26 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
                 } else {
                 lds_barrier();
                 PT(gc, 3);
-                // z = bilinear latent gather (torch's nw, ne, sw, se summation order).
-                // Wave w walks its COLS / WAVES columns; each load instruction reads one
-                // contiguous 1 KB half of a corner's 2 KB channel row (lane = 4 channels).
-#pragma unroll 4
-                for (int j = 0; j < COLS / WAVES; ++j) {
-                    const int cj = (COLS / WAVES) * wave + j;
-                    const f4 to = *reinterpret_cast<const f4 *>(gtab + cj * 8);
-                    const f4 tw = *reinterpret_cast<const f4 *>(gtab + cj * 8 + 4);
-                    f4 zh[2];
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const uint32_t ch = half * 256 + opaque_lane(lane) * 4;
-                        const f4 c0 = *reinterpret_cast<const f4 *>(a.latent + __float_as_uint(to.x) + ch);
-                        const f4 c1 = *reinterpret_cast<const f4 *>(a.latent + __float_as_uint(to.y) + ch);
-                        const f4 c2 = *reinterpret_cast<const f4 *>(a.latent + __float_as_uint(to.z) + ch);
-                        const f4 c3 = *reinterpret_cast<const f4 *>(a.latent + __float_as_uint(to.w) + ch);
-                        f4 zz;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            zz[q] = add_rn(add_rn(add_rn(mul_rn(c0[q], tw.x), mul_rn(c1[q], tw.y)),
-                                                  mul_rn(c2[q], tw.z)), mul_rn(c3[q], tw.w));
-                        if constexpr (HP) zh[half] = zz;
-                        else *reinterpret_cast<f4 *>(inbuf + cj * LDS_LD + ch) = zz;
-                        if (a.save && blk == 0 && tile * COLS + cj < P)
-                            *reinterpret_cast<f4 *>(sv_z + (v * P + tile * COLS + cj) * H + ch) = zz;
-                    }
-                    if constexpr (HP) {
-                        // column max over the wave (all 512 channels), scale, split
-                        float m = 0.f;
-#pragma unroll
-                        for (int hf = 0; hf < 2; ++hf)
-                            m = fmaxf(m, fmaxf(fmaxf(fabsf(zh[hf][0]), fabsf(zh[hf][1])),
-                                               fmaxf(fabsf(zh[hf][2]), fabsf(zh[hf][3]))));
-                        m = wave_max(m);
-                        const int e = scale_exp(m);
-                        const float sc = __builtin_ldexpf(1.f, e);
-                        put_split4(P0, P1, cj * ROWH + swz(cj, lane * 4), zh[0], sc);
-                        put_split4(P0, P1, cj * ROWH + swz(cj, 256 + lane * 4), zh[1], sc);
-                        if (lane == 0) ecol[cj] = e;
-                    }
-                }
+                float *zsave = a.save && blk == 0 ? sv_z + (v * P + tile * COLS) * H : nullptr;
+                stage_latent_gather<HP>(a.latent, gtab, inbuf, P0, P1, ecol, zsave, P - tile * COLS, wave, lane);
                 lds_barrier();
                 PT(gc, 1);
                 add_bias(x, bias + (1 + lz) * H, wave, lane, true);
                 layer_gemm<PREC, NKB, KD>(x, PK() + L.off_l512 + (int64_t)lz * L.layer_floats, gc, 1 + lz);
                 pre_publish_sync();
                 }
-                HRing<KD, NP> R0;   // fc_0's ring, primed before or during the publish (PREC 3)
-                const float *w0p = PK() + L.off_l512 + (int64_t)(lz + 1) * L.layer_floats;
-                if constexpr (HP) hring_prime(R0, w0p + opaque_lane((int)gc.ws_off));
-                f4 nb0[RTW];   // fc_0's bias rows, loaded before the publish too
-                load_bias(nb0, bias + (2 + lz) * H, wave, lane);
-                publish_relu(x, tile, blk, v * P);
-                lds_barrier();
-                PT(gc, 16);
-                set_bias(h, nb0, false);
-                layer_gemm<PREC, NKB, KD, HP>(h, PK() + L.off_l512 + (int64_t)(lz + 1) * L.layer_floats, gc, 2 + lz,
-                                          HP ? &R0 : nullptr);
-                pre_publish_sync();
-                HRing<KD, NP> R1;   // fc_1's
-                const float *w1p = PK() + L.off_l512 + (int64_t)(lz + 2) * L.layer_floats;
-                if constexpr (HP) hring_prime(R1, w1p + opaque_lane((int)gc.ws_off));
-                f4 nb1[RTW];
-                load_bias(nb1, bias + (3 + lz) * H, wave, lane);
-                publish_relu(h, tile, L.n_blocks + blk, v * P);
-                lds_barrier();
-                PT(gc, 16);
-                set_bias(x, nb1, true);
-                layer_gemm<PREC, NKB, KD, HP>(x, PK() + L.off_l512 + (int64_t)(lz + 2) * L.layer_floats, gc, 3 + lz,
-                                          HP ? &R1 : nullptr);
+                res_block(blk, lz + 1, v * P);
             }
             // ---- multi-view mean (combine_interleaved: sum over views, then / NS) --
-            if constexpr (!LEAN) if (a.ns > 1) {
-                float *xs = xs_ptr();
-                if (v == 0) {
-#pragma unroll
-                    for (int r = 0; r < RTW; ++r)
-#pragma unroll
-                        for (int c = 0; c < CT; ++c)
-                            *reinterpret_cast<f4 *>(xs + (r * CT + c) * 256) = x[r][c];
-                } else if (v < a.ns - 1) {
-#pragma unroll
-                    for (int r = 0; r < RTW; ++r)
-#pragma unroll
-                        for (int c = 0; c < CT; ++c) {
-                            f4 *ptr = reinterpret_cast<f4 *>(xs + (r * CT + c) * 256);
-                            *ptr = *ptr + x[r][c];
-                        }
-                } else {
-                    const float nsf = (float)a.ns;
-#pragma unroll
-                    for (int r = 0; r < RTW; ++r)
-#pragma unroll
-                        for (int c = 0; c < CT; ++c) {
-                            const f4 sum = *reinterpret_cast<const f4 *>(xs + (r * CT + c) * 256) + x[r][c];
-                            x[r][c] = sum / nsf;
-                        }
-                }
+            if constexpr (!LEAN) {
+                if (a.ns > 1) view_mean(x, xs_ptr(), v, a.ns);
             }
         }
         // ---- blocks after the combine layer ------------------------------------------
         for (int blk = L.ncomb; blk < L.n_blocks; ++blk) {
             const int l0 = layer_index(blk, 1, L.ncomb);
             pre_publish_sync();
-            HRing<KD, NP> R0;
-            const float *w0p = PK() + L.off_l512 + (int64_t)l0 * L.layer_floats;
-            if constexpr (HP) hring_prime(R0, w0p + opaque_lane((int)gc.ws_off));
-            f4 nb0[RTW];
-            load_bias(nb0, bias + (1 + l0) * H, wave, lane);
-            publish_relu(x, tile, blk, 0);
-            lds_barrier();
-            PT(gc, 16);
-            set_bias(h, nb0, false);
-            layer_gemm<PREC, NKB, KD, HP>(h, PK() + L.off_l512 + (int64_t)l0 * L.layer_floats, gc, 1 + l0,
-                                      HP ? &R0 : nullptr);
-            pre_publish_sync();
-            HRing<KD, NP> R1;
-            const float *w1p = PK() + L.off_l512 + (int64_t)(l0 + 1) * L.layer_floats;
-            if constexpr (HP) hring_prime(R1, w1p + opaque_lane((int)gc.ws_off));
-            f4 nb1[RTW];
-            load_bias(nb1, bias + (2 + l0) * H, wave, lane);
-            publish_relu(h, tile, L.n_blocks + blk, 0);
-            lds_barrier();
-            PT(gc, 16);
-            set_bias(x, nb1, true);
-            layer_gemm<PREC, NKB, KD, HP>(x, PK() + L.off_l512 + (int64_t)(l0 + 1) * L.layer_floats, gc, 2 + l0,
-                                      HP ? &R1 : nullptr);
+            res_block(blk, l0, 0);
         }
         // ---- lin_out(relu(x)) + head [sigmoid(rgb), relu(sigma)]: wave w < CT -> columns 16w..
         if (wave == 0) *s_next = s_in + 1 < upt ? (int)tile + 1 : grab();   // read after the closing barrier
@@ -882,8 +817,9 @@ int64_t mlp_save_floats(const pnr_mlp_desc &d, int64_t n_points) {
 }
 
 size_t mlp_xsum_bytes(int ns) {
-    (void)ns;  // x park + multi-view sum, one pair of 128 KB regions per resident workgroup,
-               // then the 8 per-XCD tile counters (512 B)
+    (void)ns;  // one pair of 128 KB regions per resident workgroup (the first unused, the second the
+               // multi-view sum; the size is observable: pnr_point_query_workspace_bytes), then the
+               // 8 per-XCD tile counters (512 B)
     return sizeof(float) * (size_t)device_cu_count() * 2 * mlpk::COLS * mlpk::H + 512;
 }
 
@@ -917,31 +853,28 @@ static void select_kernel(bool pz, bool march, bool lean, unsigned grid, size_t 
 
 // Launch the fused model over c.n_points points (render mode if c.rays != nullptr).
 int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const PointMlpCall &c, hipStream_t st) {
-    const float *const proj = c.proj, *const rays = c.rays, *const save = c.save;
     const MarchCfg *const march = c.march;
-    const int K = c.K;
-    const int64_t n_points = c.n_points;
-    if (n_points == 0) return PNR_OK;
-    if (d.precision == PNR_PREC_F16 && (!proj || save))
+    if (c.n_points == 0) return PNR_OK;
+    if (d.precision == PNR_PREC_F16 && (!c.proj || c.save))
         return fail(PNR_ERR_UNSUPPORTED, "precision 1 (f16) is inference only on the projected-latent path: it "
                     "needs the latent projection and takes no activation save; use precision 3 (f16x3)");
-    if (proj && save) return fail(PNR_ERR_UNSUPPORTED, "the activation save (training) needs the latent gather path");
-    if (march && (!rays || save || (march->kpt != 1 && march->kpt != 2) || K != mlpk::COLS * march->kpt ||
-                  n_points % K != 0 || (march->kf > 0 && (K > 64 || march->n_sort > 128 || K + march->kf > march->n_sort))))
+    if (c.proj && c.save) return fail(PNR_ERR_UNSUPPORTED, "the activation save (training) needs the latent gather path");
+    if (march && (!c.rays || c.save || (march->kpt != 1 && march->kpt != 2) || c.K != mlpk::COLS * march->kpt ||
+                  c.n_points % c.K != 0 || (march->kf > 0 && (c.K > 64 || march->n_sort > 128 || c.K + march->kf > march->n_sort))))
         return fail(PNR_ERR_INVALID, "point_mlp: fused march needs K = 64 kpt (kpt 1 or 2) and kc + kf <= 128");
     if (march && march->single &&
-        (!proj || !march->packed_f || !march->proj_f || march->kf <= 0 || march->kpt != 1 ||
-         march->kpt_f * mlpk::COLS != K + march->kf || (march->kpt_f != 1 && march->kpt_f != 2) ||
-         !march->rgb_f || !march->depth_f || n_points % (K + march->kpt_f * mlpk::COLS) != 0))
+        (!c.proj || !march->packed_f || !march->proj_f || march->kf <= 0 || march->kpt != 1 ||
+         march->kpt_f * mlpk::COLS != c.K + march->kf || (march->kpt_f != 1 && march->kpt_f != 2) ||
+         !march->rgb_f || !march->depth_f || c.n_points % (c.K + march->kpt_f * mlpk::COLS) != 0))
         return fail(PNR_ERR_INVALID, "point_mlp: the single-launch march needs kc = 64, kc + kf = 64 kpt_f, both "
                     "packs and projections, fine outputs, and n_points = n_rays (kc + kc + kf)");
     mlpk::Args a = {};
     a.packed = static_cast<const float *>(c.packed);
     a.L = mlpk::make_layout(d);
-    a.render_mode = rays != nullptr;
-    a.rays = rays; a.zs = c.z; a.K = K; a.rays_per_obj = c.rays_per_obj;
+    a.render_mode = c.rays != nullptr;
+    a.rays = c.rays; a.zs = c.z; a.K = c.K; a.rays_per_obj = c.rays_per_obj;
     a.xyz = c.xyz; a.dirs = c.dirs; a.points_per_obj = c.points_per_obj;
-    a.n_points = n_points;
+    a.n_points = c.n_points;
     a.latent = sc.latent; a.cams = sc.cams;
     a.ns = sc.n_views; a.hl = sc.latent_h; a.wl = sc.latent_w;
     a.img_w = sc.image_w; a.img_h = sc.image_h;
@@ -949,9 +882,9 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const PointMlpC
     a.xsum = c.xsum;
     a.march = march != nullptr;
     if (march) a.m = *march;
-    a.n_tiles = (n_points + mlpk::COLS - 1) / mlpk::COLS;
+    a.n_tiles = (c.n_points + mlpk::COLS - 1) / mlpk::COLS;
     a.save = c.save;
-    a.proj = proj;
+    a.proj = c.proj;
     a.proj_stride = (int64_t)sc.n_obj * sc.n_views * sc.latent_h * sc.latent_w * mlpk::H;
     const int cus = device_cu_count();
     if (a.n_tiles >= (1ll << 31)) return fail(PNR_ERR_UNSUPPORTED, "more than 2^31 point tiles in one launch");
@@ -961,10 +894,10 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const PointMlpC
     // The lean instantiation: a render (rays) of ONE source view on the projected latent by a
     // per-pass fused march (modes 1 and 2, not the single launch), no activation save, f16x3 or
     // f16.  Every other descriptor takes the general instantiations.
-    const bool lean = g_mlp_lean.load(std::memory_order_relaxed) && mlpk::is_h(d.precision) && proj && march &&
-                      !march->single && rays && sc.n_views == 1 && !save;
+    const bool lean = g_mlp_lean.load(std::memory_order_relaxed) && mlpk::is_h(d.precision) && c.proj && march &&
+                      !march->single && c.rays && sc.n_views == 1 && !c.save;
     g_mlp_last_kernel.store(lean ? PNR_MLP_KERNEL_LEAN : PNR_MLP_KERNEL_GENERAL, std::memory_order_relaxed);
-    const bool pz = proj != nullptr, fused = march != nullptr;
+    const bool pz = c.proj != nullptr, fused = march != nullptr;
     const size_t lds = lean ? mlpk::lds_bytes_lean(mlpk::fwd_lds(true))   // the march map + the lean table
                             : mlpk::lds_bytes(mlpk::fwd_lds(mlpk::is_h(d.precision)), fused);
     switch (d.precision) {

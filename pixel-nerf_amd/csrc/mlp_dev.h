@@ -1,5 +1,5 @@
 // Device building blocks that k_point_mlp (mlp.hip) and k_mlp_bwd (mlp_bwd.hip) inline: the three
-// GEMM families, the fp16 weight ring, the relu publish, bias helpers, the projected-latent stage,
+// GEMM families, the fp16 weight ring, the relu publish, bias helpers, the projected-latent and latent-gather stages,
 // the activation-save stores and the tile claim.
 #pragma once
 #include "pnr_diag.h"
@@ -602,6 +602,55 @@ __device__ __forceinline__ void stage_proj_runs(const float *__restrict__ pz, co
         a = d;
         b = e;
         c = f;
+    }
+}
+// stage_proj_runs' twin on the latent itself (the lin_z GEMM follows): z = the bilinear sample of
+// the latent's four corner rows (torch's nw, ne, sw, se summation order) of every column, written
+// as the GEMM's input image -- fp32 image[column][LDS_LD], or (HP) scaled by the column's maximum
+// over all 512 channels and split into P0 / P1 with its exponent in ecol.  Wave w walks its
+// COLS / WAVES columns; each load instruction reads one contiguous 1 KB half of a corner's 2 KB
+// channel row (lane = 4 channels).  zsave (training forward, or NULL): the tile's rows of the
+// activation save's z region, of which the first n_valid are points.  Callers barrier before
+// (the image is free) and after.
+template <bool HP>
+__device__ __forceinline__ void stage_latent_gather(const float *__restrict__ latent, const float *gtab, float *image,
+                                                    _Float16 *P0, _Float16 *P1, int *ecol, float *zsave,
+                                                    int64_t n_valid, int wave, int lane) {
+#pragma unroll 4
+    for (int j = 0; j < COLS / WAVES; ++j) {
+        const int cj = (COLS / WAVES) * wave + j;
+        const f4 to = *reinterpret_cast<const f4 *>(gtab + cj * 8);
+        const f4 tw = *reinterpret_cast<const f4 *>(gtab + cj * 8 + 4);
+        f4 zh[2];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const uint32_t ch = half * 256 + opaque_lane(lane) * 4;
+            const f4 c0 = *reinterpret_cast<const f4 *>(latent + __float_as_uint(to.x) + ch);
+            const f4 c1 = *reinterpret_cast<const f4 *>(latent + __float_as_uint(to.y) + ch);
+            const f4 c2 = *reinterpret_cast<const f4 *>(latent + __float_as_uint(to.z) + ch);
+            const f4 c3 = *reinterpret_cast<const f4 *>(latent + __float_as_uint(to.w) + ch);
+            f4 zz;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                zz[q] = add_rn(add_rn(add_rn(mul_rn(c0[q], tw.x), mul_rn(c1[q], tw.y)), mul_rn(c2[q], tw.z)),
+                               mul_rn(c3[q], tw.w));
+            if constexpr (HP) zh[half] = zz;
+            else *reinterpret_cast<f4 *>(image + cj * LDS_LD + ch) = zz;
+            if (zsave && cj < n_valid) *reinterpret_cast<f4 *>(zsave + (int64_t)cj * H + ch) = zz;
+        }
+        if constexpr (HP) {
+            // column max over the wave (all 512 channels), scale, split
+            float m = 0.f;
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf)
+                m = fmaxf(m, fmaxf(fmaxf(fabsf(zh[hf][0]), fabsf(zh[hf][1])), fmaxf(fabsf(zh[hf][2]), fabsf(zh[hf][3]))));
+            m = wave_max(m);
+            const int e = scale_exp(m);
+            const float sc = __builtin_ldexpf(1.f, e);
+            put_split4(P0, P1, cj * ROWH + swz(cj, lane * 4), zh[0], sc);
+            put_split4(P0, P1, cj * ROWH + swz(cj, 256 + lane * 4), zh[1], sc);
+            if (lane == 0) ecol[cj] = e;
+        }
     }
 }
 // x[r][c] += stage rows of this wave (column 16c + cl, rows 16 (RTW wave + r) + 4g ..)
