@@ -46,12 +46,6 @@ int device_cu_count() {
     return n;
 }
 
-// true if any of the pointers has a bit of `mask` (alignment - 1) set; NULL passes
-template <typename... T>
-static bool misaligned(uintptr_t mask, const T *...p) {
-    return ((reinterpret_cast<uintptr_t>(p) | ...) & mask) != 0;
-}
-
 // PNR_ERR_WORKSPACE if the call `who` needs `need` bytes and the caller's workspace is absent or smaller
 static int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, size_t need) {
     if (need && (!workspace || workspace_bytes < need))
@@ -266,8 +260,20 @@ int pnr_mlp_backward_views(const pnr_mlp_desc *desc, const void *packed, const v
         return fail(PNR_ERR_INVALID, "pnr_mlp_backward: NULL argument");
     if (misaligned(15, lin_out_w, save, d_o, dy, d_zlat))
         return fail(PNR_ERR_INVALID, "pnr_mlp_backward: buffers must be 16-byte aligned");
-    return launch_mlp_bwd(*desc, packed, packed_t, lin_out_w, save, d_o, n_points, dy, d_zlat, (hipStream_t)stream,
-                          d_bias, workspace, workspace_bytes, n_views);
+    MlpBwdCall c;
+    c.packed = packed;
+    c.packed_t = packed_t;
+    c.w_out = lin_out_w;
+    c.save = save;
+    c.d_o = d_o;
+    c.n_points = n_points;
+    c.n_views = n_views;
+    c.dy = dy;
+    c.dzlat = d_zlat;
+    c.d_bias = d_bias;
+    c.ws = workspace;
+    c.ws_bytes = workspace_bytes;
+    return launch_mlp_bwd(*desc, c, (hipStream_t)stream);
 }
 
 size_t pnr_weight_grad_workspace_bytes(int32_t n_layers, int64_t n_points) {
@@ -277,15 +283,15 @@ size_t pnr_weight_grad_workspace_bytes(int32_t n_layers, int64_t n_points) {
 int pnr_weight_grad(const float *const *dy, const float *const *x, float *const *d_weight, int32_t n_layers,
                     int64_t n_points, void *workspace, size_t workspace_bytes, pnr_stream_t stream) {
     if (!dy || !x || !d_weight) return fail(PNR_ERR_INVALID, "pnr_weight_grad: NULL argument");
-    return launch_wgrad(dy, x, d_weight, n_layers, n_points, workspace, workspace_bytes, (hipStream_t)stream,
-                        PNR_WGRAD_F16X3);
+    return launch_wgrad(dy, x, d_weight, n_layers, n_points, workspace, workspace_bytes, PNR_WGRAD_F16X3,
+                        (hipStream_t)stream);
 }
 
 int pnr_weight_grad_arith(const float *const *dy, const float *const *x, float *const *d_weight, int32_t n_layers,
                           int64_t n_points, int32_t arith, void *workspace, size_t workspace_bytes,
                           pnr_stream_t stream) {
     if (!dy || !x || !d_weight) return fail(PNR_ERR_INVALID, "pnr_weight_grad_arith: NULL argument");
-    return launch_wgrad(dy, x, d_weight, n_layers, n_points, workspace, workspace_bytes, (hipStream_t)stream, arith);
+    return launch_wgrad(dy, x, d_weight, n_layers, n_points, workspace, workspace_bytes, arith, (hipStream_t)stream);
 }
 
 // workspace layout of pnr_render_forward

@@ -51,6 +51,34 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// this lane's fragment of row tile r of its wave in row `row` of a [row][512] matrix: channels
+// 16 (RTW wave + r) + 4 g .. + 3
+__device__ __forceinline__ const f4 *frag_at(const float *base, int64_t row, int wave, int r, int g) {
+    return reinterpret_cast<const f4 *>(base + row * H + 16 * (RTW * wave + r) + 4 * g);
+}
+__device__ __forceinline__ f4 *frag_at(float *base, int64_t row, int wave, int r, int g) {
+    return const_cast<f4 *>(frag_at(static_cast<const float *>(base), row, wave, r, g));
+}
+
+__device__ __forceinline__ void acc_zero(Acc &a) {
+#pragma unroll
+    for (int r = 0; r < RTW; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) a[r][c] = f4{0.f, 0.f, 0.f, 0.f};
+}
+__device__ __forceinline__ void acc_add(Acc &a, const Acc &b) {
+#pragma unroll
+    for (int r = 0; r < RTW; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) a[r][c] += b[r][c];
+}
+__device__ __forceinline__ void acc_div(Acc &a, float d) {
+#pragma unroll
+    for (int r = 0; r < RTW; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) a[r][c] = a[r][c] / d;
+}
+
 // this wave's rows of acc -> slot [point][512] (points < n_points)
 __device__ __forceinline__ void store_rows(const Acc &acc, float *slot, int64_t tile, int64_t n_points,
                                            int wave, int lane, float *bs = nullptr, bool first = false) {
@@ -61,8 +89,7 @@ __device__ __forceinline__ void store_rows(const Acc &acc, float *slot, int64_t 
         const int64_t p = tile * COLS + 16 * c + cl;
         if (p >= n_points) continue;
 #pragma unroll
-        for (int r = 0; r < RTW; ++r)
-            *reinterpret_cast<f4 *>(slot + p * H + 16 * (RTW * wave + r) + 4 * g) = acc[r][c];
+        for (int r = 0; r < RTW; ++r) *frag_at(slot, p, wave, r, g) = acc[r][c];
     }
     if (bs) {   // bias gradient: this tile's column sums of the wave's rows, added to bs
         f4 sr[RTW];
@@ -79,9 +106,38 @@ __device__ __forceinline__ void store_rows(const Acc &acc, float *slot, int64_t 
         if (cl == 0) {
 #pragma unroll
             for (int r = 0; r < RTW; ++r) {
-                f4 *q = reinterpret_cast<f4 *>(bs + 16 * (RTW * wave + r) + 4 * g);
+                f4 *q = frag_at(bs, 0, wave, r, g);
                 *q = first ? sr[r] : *q + sr[r];
             }
+        }
+    }
+}
+// store_rows' twin: acc <- this wave's rows of slot (a point past n_points reads the last point)
+__device__ __forceinline__ void load_rows(Acc &acc, const float *slot, int64_t tile, int64_t n_points, int wave,
+                                          int lane) {
+    lane = opaque_lane(lane);
+    const int g = lane >> 4, cl = lane & 15;
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        const int64_t p = tile * COLS + 16 * c + cl;
+        const int64_t pc = p < n_points ? p : n_points - 1;
+#pragma unroll
+        for (int r = 0; r < RTW; ++r) acc[r][c] = *frag_at(slot, pc, wave, r, g);
+    }
+}
+// store_rows, accumulating, on rows row0 + p: slot = first ? acc : slot + acc (points < n_points)
+__device__ __forceinline__ void add_rows(const Acc &acc, float *slot, int64_t row0, int64_t tile, int64_t n_points,
+                                         int wave, int lane, bool first) {
+    lane = opaque_lane(lane);
+    const int g = lane >> 4, cl = lane & 15;
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        const int64_t p = tile * COLS + 16 * c + cl;
+        if (p >= n_points) continue;
+#pragma unroll
+        for (int r = 0; r < RTW; ++r) {
+            f4 *q = frag_at(slot, row0 + p, wave, r, g);
+            *q = first ? acc[r][c] : *q + acc[r][c];
         }
     }
 }
@@ -120,8 +176,7 @@ __device__ __forceinline__ void relu_mask(Acc &acc, const u2m (&mk)[CT], int64_t
 
 __global__ __launch_bounds__(NTHR) void k_mlp_bwd(BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, cl = lane & 15;
     const Layout &L = a.L;
@@ -140,14 +195,9 @@ __global__ __launch_bounds__(NTHR) void k_mlp_bwd(BwdArgs a) {
     gc.pb0 = P0 + cl * ROWH + swz(cl, 8 * g);
     gc.pb1 = P1 + cl * ROWH + swz(cl, 8 * g);
     gc.ecol = ecol;
-    gc.fair.prog = nullptr;
+    gc.fair.prog = reinterpret_cast<int *>(smem + M.prog);
     gc.fair.wave = wave;
-    gc.fair.it = 0;
-    gc.fair.mate = 0;
-    {
-        gc.fair.prog = reinterpret_cast<int *>(smem + M.prog);
-        if (threadIdx.x < WAVES) gc.fair.prog[threadIdx.x] = 0;
-    }
+    if (threadIdx.x < WAVES) gc.fair.prog[threadIdx.x] = 0;
     gc.wave = wave;
     gc.lane = lane;
     // relu sign masks of the forward: slot b: relu(x_b), nb + b: relu(h_b), 2 nb: x_f; every
@@ -167,28 +217,19 @@ __global__ __launch_bounds__(NTHR) void k_mlp_bwd(BwdArgs a) {
         relu_store_split<false>(acc, P0, P1, cmax, ecol, wave, lane, gc.ecl);
         __syncthreads();
     };
-    auto zero = [](Acc &acc) {
-#pragma unroll
-        for (int r = 0; r < RTW; ++r)
-#pragma unroll
-            for (int c = 0; c < CT; ++c) acc[r][c] = f4{0.f, 0.f, 0.f, 0.f};
-    };
-    auto layer = [&](int li) { return a.packed_t + (int64_t)li * L.layer_floats; };
 
     Acc x, h;
     // segments of the chain: NS == 1: blocks nb-1 .. 0; else blocks nb-1 .. nc per point, then
     // nc-1 .. 0 once per view on its rows v P + p
     const int n_seg = a.ns == 1 ? 1 : 1 + a.ns;
     for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        const bool first_tile = tile == blockIdx.x;
         {   // dx = (d_o W_out) . [x_f > 0]
             load_mask(mk, mask_slot(2 * nb, 0), tile, P, wave, lane);
             f4 wo[4][RTW];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int r = 0; r < RTW; ++r)
-                    wo[j][r] = *reinterpret_cast<const f4 *>(a.w_out + j * H + 16 * (RTW * wave + r) + 4 * g);
+                for (int r = 0; r < RTW; ++r) wo[j][r] = *frag_at(a.w_out, j, wave, r, g);
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 const int64_t p = tile * COLS + 16 * c + cl;
@@ -204,63 +245,35 @@ __global__ __launch_bounds__(NTHR) void k_mlp_bwd(BwdArgs a) {
             const int b_hi = sgi == 0 ? nb : nc, b_lo = sgi == 0 ? nc : 0;
             const int64_t row0 = v > 0 ? (int64_t)v * P : 0;
             // the first store of the workgroup to the bias partials of these slots
-            const bool first = first_tile && v <= 0;
-            if (v == 0) {   // torch.mean's backward: dL/d(mean) / NS to every view
-                const float inv = (float)a.ns;
-#pragma unroll
-                for (int r = 0; r < RTW; ++r)
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) x[r][c] = x[r][c] / inv;
-            } else if (v > 0 && nc > 0) {   // the same, as view 0 stored it (this lane's own rows)
-                const float *src = dy_slot(nb + nc, 0);
-                const int ln = opaque_lane(lane), gz = ln >> 4;
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const int64_t p = tile * COLS + 16 * c + (ln & 15);
-                    const int64_t pc = p < P ? p : P - 1;
-#pragma unroll
-                    for (int r = 0; r < RTW; ++r)
-                        x[r][c] = *reinterpret_cast<const f4 *>(src + pc * H + 16 * (RTW * wave + r) + 4 * gz);
-                }
-            }
+            const bool first = tile == blockIdx.x && v <= 0;
+            if (v == 0)   // torch.mean's backward: dL/d(mean) / NS to every view
+                acc_div(x, (float)a.ns);
+            else if (v > 0 && nc > 0)   // the same, as view 0 stored it (this lane's own rows)
+                load_rows(x, dy_slot(nb + nc, 0), tile, P, wave, lane);
+            // one step of the chain: h = W_li^T . image, then . [saved activation of mask slot mi > 0]
+            // if masked (the mask words are loaded before the GEMM and land during it)
+            auto chain_step = [&](int li, bool masked, int mi = 0) {
+                acc_zero(h);
+                if (masked) load_mask(mk, mask_slot(mi, row0), tile, P, wave, lane);
+                layer_gemm<3, NKB, H_DIST, true>(h, a.packed_t + (int64_t)li * L.layer_floats, gc, 1 + li);
+                if (masked) relu_mask(h, mk, tile, P, lane);
+            };
             bool published = false;
             for (int b = b_hi - 1; b >= b_lo; --b) {
                 if (!published) publish(x);
                 store_rows(x, dy_slot(nb + 1 + b, row0), tile, P, wave, lane, bs_slot(nb + 1 + b), first);
                 const int l1 = layer_index(b, 2, L.n_linz), l0 = layer_index(b, 1, L.n_linz);
-                zero(h);
-                load_mask(mk, mask_slot(nb + b, row0), tile, P, wave, lane);   // lands during the GEMM
-                layer_gemm<3, NKB, H_DIST, true>(h, layer(l1), gc, 1 + l1);
-                relu_mask(h, mk, tile, P, lane);
+                chain_step(l1, true, nb + b);   // fc_1
                 store_rows(h, dy_slot(b, row0), tile, P, wave, lane, bs_slot(b), first);
                 publish(h);
-                zero(h);
-                load_mask(mk, mask_slot(b, row0), tile, P, wave, lane);
-                layer_gemm<3, NKB, H_DIST, true>(h, layer(l0), gc, 1 + l0);
-                relu_mask(h, mk, tile, P, lane);
-#pragma unroll
-                for (int r = 0; r < RTW; ++r)
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) x[r][c] += h[r][c];
+                chain_step(l0, true, b);   // fc_0
+                acc_add(x, h);
                 published = false;
                 if (b < L.n_linz) {
                     publish(x);
                     published = true;
-                    const int lz = layer_index(b, 0, L.n_linz);
-                    zero(h);
-                    layer_gemm<3, NKB, H_DIST, true>(h, layer(lz), gc, 1 + lz);
-                    const bool zfirst = b == L.n_linz - 1;
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        const int ln = opaque_lane(lane), gz = ln >> 4;
-                        const int64_t p = tile * COLS + 16 * c + (ln & 15);
-                        if (p >= P) continue;
-#pragma unroll
-                        for (int r = 0; r < RTW; ++r) {
-                            f4 *q = reinterpret_cast<f4 *>(a.dzlat + (row0 + p) * H + 16 * (RTW * wave + r) + 4 * gz);
-                            *q = zfirst ? h[r][c] : *q + h[r][c];
-                        }
-                    }
+                    chain_step(layer_index(b, 0, L.n_linz), false);   // lin_z
+                    add_rows(h, a.dzlat, row0, tile, P, wave, lane, b == L.n_linz - 1);
                 }
             }
             // dY(lin_in) belongs to the segment that ends the chain: with NS > 1 a view's, never the
@@ -315,41 +328,37 @@ size_t mlp_bwd_workspace_bytes(const pnr_mlp_desc &d, int64_t n_points) {
     return sizeof(float) * (size_t)mlp_bwd_grid(n_points) * (2 * d.n_blocks + 1) * mlpk::H;
 }
 
-int launch_mlp_bwd(const pnr_mlp_desc &d, const void *packed, const void *packed_t, const float *w_out,
-                   const float *save, const float *d_o, int64_t n_points, float *dy, float *dzlat, hipStream_t st,
-                   float *d_bias, void *ws, size_t ws_bytes, int n_views) {
+int launch_mlp_bwd(const pnr_mlp_desc &d, const MlpBwdCall &c, hipStream_t st) {
     int rc = mlp_check_desc(d);
     if (rc) return rc;
     if (d.precision != PNR_PREC_F16X3)
         return fail(PNR_ERR_UNSUPPORTED, "the fused MLP backward implements precision 3 (f16x3); got %d", d.precision);
     mlpk::BwdArgs a = {};
     a.L = mlpk::make_layout(d);
-    if (a.L.n_linz > 0 && !dzlat) return fail(PNR_ERR_INVALID, "mlp backward: d_zlat is required (n_linz > 0)");
-    if (n_points == 0) return PNR_OK;
-    a.hdr = static_cast<const float *>(packed);
-    a.packed_t = static_cast<const float *>(packed_t);
-    a.w_out = w_out;
-    a.save = save;
-    a.d_o = d_o;
-    a.dy = dy;
-    a.dzlat = dzlat;
-    a.n_points = n_points;
-    a.n_tiles = (n_points + mlpk::COLS - 1) / mlpk::COLS;
-    if (n_views < 1) return fail(PNR_ERR_INVALID, "mlp backward: n_views < 1");
-    a.ns = n_views;
-    const int64_t grid = mlp_bwd_grid(n_points);
-    if (d_bias) {
-        const size_t need = mlp_bwd_workspace_bytes(d, n_points);
-        if (!ws || ws_bytes < need) return fail(PNR_ERR_WORKSPACE, "mlp backward: workspace %zu < %zu", ws_bytes, need);
-        a.bsum = static_cast<float *>(ws);
-    }
+    if (a.L.n_linz > 0 && !c.dzlat) return fail(PNR_ERR_INVALID, "mlp backward: d_zlat is required (n_linz > 0)");
+    if (c.n_points == 0) return PNR_OK;
+    const size_t need = mlp_bwd_workspace_bytes(d, c.n_points);
+    if (c.d_bias && (!c.ws || c.ws_bytes < need))
+        return fail(PNR_ERR_WORKSPACE, "mlp backward: workspace %zu < %zu", c.ws_bytes, need);
+    a.hdr = static_cast<const float *>(c.packed);
+    a.packed_t = static_cast<const float *>(c.packed_t);
+    a.w_out = c.w_out;
+    a.save = c.save;
+    a.d_o = c.d_o;
+    a.dy = c.dy;
+    a.dzlat = c.dzlat;
+    a.bsum = c.d_bias ? static_cast<float *>(c.ws) : nullptr;
+    a.n_points = c.n_points;
+    a.n_tiles = (c.n_points + mlpk::COLS - 1) / mlpk::COLS;
+    a.ns = c.n_views;
+    const int64_t grid = mlp_bwd_grid(c.n_points);
     const size_t lds = mlpk::lds_bytes(mlpk::bwd_lds());
     hipLaunchKernelGGL(mlpk::k_mlp_bwd, dim3((unsigned)grid), dim3(mlpk::NTHR), lds, st, a);
     if (!launch_ok("mlp_bwd")) return PNR_ERR_HIP;
-    if (d_bias) {
+    if (c.d_bias) {
         const int n = (2 * d.n_blocks + 1) * mlpk::H;
         hipLaunchKernelGGL(mlpk::k_bias_reduce, dim3((unsigned)((n + 63) / 64)), dim3(64 * mlpk::BIAS_SLICES), 0,
-                           st, a.bsum, (int)grid, n, d_bias);
+                           st, a.bsum, (int)grid, n, c.d_bias);
         if (!launch_ok("bias_reduce")) return PNR_ERR_HIP;
     }
     return PNR_OK;

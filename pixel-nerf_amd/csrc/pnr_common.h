@@ -28,6 +28,12 @@ inline bool launch_ok(const char *what) {
     return true;
 }
 
+// true if any of the pointers has a bit of `mask` (alignment - 1) set; NULL passes
+template <typename... T>
+inline bool misaligned(uintptr_t mask, const T *...p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & mask) != 0;
+}
+
 // workspace regions start on 256-byte boundaries
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 

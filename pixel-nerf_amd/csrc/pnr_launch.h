@@ -1,6 +1,8 @@
 // Host launchers and size helpers behind the C ABI (abi.cpp), each declared once with its default
 // arguments and with the parameter names of its definition.  Every .hip file that defines one
 // includes this header, so a definition whose types drift from its declaration fails to compile.
+// The fused MLP's launchers take their buffers as a struct of named fields (PointMlpCall for the
+// forward, MlpBwdCall for the training backward), then the stream.
 #pragma once
 #include "pnr_common.h"
 
@@ -56,14 +58,27 @@ int launch_point_mlp(const pnr_scene &sc, const pnr_mlp_desc &d, const PointMlpC
 int mlp_set_lean(int on);   // the lean instantiation's process-wide switch (returns the previous setting)
 int mlp_last_kernel();      // PNR_MLP_KERNEL_* of the last launch_point_mlp
 // mlp_bwd.hip
-int launch_mlp_bwd(const pnr_mlp_desc &d, const void *packed, const void *packed_t, const float *w_out,
-                   const float *save, const float *d_o, int64_t n_points, float *dy, float *dzlat, hipStream_t st,
-                   float *d_bias, void *ws, size_t ws_bytes, int n_views);
+// One launch of the fused f16x3 backward chain over n_points points with n_views source views.
+struct MlpBwdCall {
+    const void *packed = nullptr;      // forward pack (header: weight scale exponents)
+    const void *packed_t = nullptr;    // k_pack_f16_t output (pnr_mlp_pack_t)
+    const float *w_out = nullptr;      // lin_out weight (4 x 512, fp32)
+    const float *save = nullptr;       // forward activation save
+    const float *d_o = nullptr;        // (n_points, 4) gradient of the pre-head output
+    int64_t n_points = 0;
+    int n_views = 1;                   // source views per point (the save's view rows)
+    float *dy = nullptr;               // (2 nb + 1) x (n_views n_points) x 512 output gradients per layer
+    float *dzlat = nullptr;            // (n_views n_points, 512) gradient of the sampled latent (n_linz > 0)
+    float *d_bias = nullptr;           // NULL, or (2 nb + 1) x 512 column sums of each dy slot
+    void *ws = nullptr;                // workspace of mlp_bwd_workspace_bytes() (d_bias only)
+    size_t ws_bytes = 0;
+};
+int launch_mlp_bwd(const pnr_mlp_desc &d, const MlpBwdCall &c, hipStream_t st);
 size_t mlp_bwd_workspace_bytes(const pnr_mlp_desc &d, int64_t n_points);
 // wgrad.hip
 size_t wgrad_workspace_bytes(int n_jobs, int64_t n_points);
 int launch_wgrad(const float *const *dy, const float *const *x, float *const *g, int n_jobs, int64_t n_points,
-                 void *ws, size_t ws_bytes, hipStream_t st, int arith);
+                 void *ws, size_t ws_bytes, int arith, hipStream_t st);
 // encoder.hip
 int launch_fold_bn(const pnr_bn_fold *folds, int n_folds, int64_t max_elems, hipStream_t st);
 int launch_latent_cl_bwd(const float *g, float *const *d_maps, const int32_t *channels, const int32_t *heights,

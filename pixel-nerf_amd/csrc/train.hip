@@ -8,8 +8,8 @@
 //                     d(latent feature z) -> d latent (bilinear scatter, grid_sample
 //                     backward, encoder.py:102-108) and d z_sample (through the PE,
 //                     code.py:38, and the projection, models.py:206-212)
-// The ResnetFC backward runs as plain per-layer GEMMs on the saved activations
-// (pnr/train.py).
+// The ResnetFC backward is mlp_bwd.hip (the fused f16x3 chain) and wgrad.hip (weight gradients);
+// the fp32 / bf16 models run it as per-layer torch GEMMs on the saved activations (pnr/train.py).
 #include "pnr_common.h"
 #include "pnr_launch.h"
 
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(
 }
 
 // ---------------------------------------------------------------------------
-// per-point input backward (NS == 1).  One wave per run of RUN consecutive points
+// per-point input backward, every source view in turn.  One wave per run of RUN consecutive points
 // (o + z d of ray b, in sample order):
 //   d latent[corner][c] += w_corner d_zlat[c]        (channels-last; see below)
 //   d z_sample = d . R^T (d x_rot)   with d x_rot from

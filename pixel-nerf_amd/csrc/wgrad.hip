@@ -80,50 +80,113 @@ __device__ __forceinline__ int prow(int p) { return (p & ~12) | ((p & 4) << 1) |
 // MFMA operand of 16 columns: lane l receives column c0 + (l & 15), points 8 (l >> 4) ..
 // + 7.  `base` = image + 2 c0 bytes; lo / hi = the lane's byte offsets of its points
 // 8g + q and 8g + 4 + q (q = (l & 15) >> 2) plus 8 ((l & 3)) within the 16 columns.
-__device__ __forceinline__ bf8 tr_frag(const char *base, int lo, int hi) {
+// V = bf8 or h8: the same 16 bytes either way.
+template <typename V>
+__device__ __forceinline__ V tr_frag(const char *base, int lo, int hi) {
     const s4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(base + lo));
     const s4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(base + hi));
     typedef short s8 __attribute__((ext_vector_type(8)));
     const s8 v = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return __builtin_bit_cast(bf8, v);
+    return __builtin_bit_cast(V, v);
+}
+
+// Shared by both kernels.  blockIdx -> (unit u = (job, chunk), block (nb, kb) of its 4); the 4 blocks of a unit share an
+// XCD.  Points [p0, p1) are the unit's chunk.
+struct Unit {
+    int u, job, chunk, nb, kb;
+    int64_t p0, p1;
+};
+// false for the workgroups past the last unit (the whole workgroup: uniform)
+__device__ __forceinline__ bool unit_of(const Args &a, Unit &t) {
+    const int bid = blockIdx.x, xcd = bid & 7, local = bid >> 3, b4 = local & 3;
+    t.u = 8 * (local >> 2) + xcd;
+    if (t.u >= a.n_units) return false;
+    t.job = t.u / a.chunks, t.chunk = t.u % a.chunks;
+    t.nb = b4 & 1, t.kb = b4 >> 1;
+    t.p0 = (int64_t)t.chunk * a.chunk_points;
+    t.p1 = t.p0 + a.chunk_points < a.n_points ? t.p0 + a.chunk_points : a.n_points;
+    return true;
+}
+
+// staging role of a thread: point r of the step, columns 8j .. 8j+7 and 128+8j .. 128+8j+7 (j = t & 15)
+// of the block's dY and X; woff = its byte offset in an image (+ 256 for the second 8 columns)
+struct Stage {
+    int r, jc, woff;
+    const float *dsrc, *xsrc;
+};
+__device__ __forceinline__ Stage stage_of(const Args &a, const Unit &t, int tid) {
+    Stage s;
+    s.r = tid >> 4, s.jc = tid & 15;
+    s.dsrc = a.dy[t.job] + t.nb * BM + 8 * s.jc;
+    s.xsrc = a.x[t.job] + t.kb * BM + 8 * s.jc;
+    s.woff = PITCH * prow(s.r) + 16 * s.jc;
+    return s;
+}
+
+// the thread's 16 + 16 floats of point row p: 4 f4 of dY and 4 of X.  Returns ok = the row is a
+// point of the chunk; a row past it reads row 0 (an in-bounds address) and is staged as zeros.
+__device__ __forceinline__ bool load_row(const Stage &s, int64_t p, int64_t p1, f4 (&d)[4], f4 (&x)[4]) {
+    const bool ok = p < p1;
+    const int64_t pc = ok ? p : 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int col = 128 * (i >> 1) + 4 * (i & 1);
+        d[i] = *reinterpret_cast<const f4 *>(s.dsrc + pc * H + col);
+        x[i] = *reinterpret_cast<const f4 *>(s.xsrc + pc * H + col);
+    }
+    return ok;
+}
+
+// a wave's 128 x 64 of the block: 8 x 4 tiles of 16 x 16
+typedef f4 BlockAcc[8][4];
+__device__ __forceinline__ void acc_zero(BlockAcc &acc) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+}
+
+// a lane's place in its wave's tiles: the wave's corner (n0, k0) of the block, the lane's C rows
+// 4 g + e and column li of a tile, and its transpose-read offsets t_lo / t_hi
+struct TileLane {
+    int n0, k0, g, li, t_lo, t_hi;
+};
+// the lane's transpose-read byte offset of points 8g + 4 half + q, column pair pp
+__device__ __forceinline__ int tr_off(int lane, int half) {
+    const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
+    return PITCH * prow(8 * g + 4 * half + q) + 8 * pp;
+}
+__device__ __forceinline__ TileLane tile_lane(int wave, int lane) {
+    return TileLane{128 * (wave & 1), 64 * (wave >> 1), lane >> 4, lane & 15, tr_off(lane, 0), tr_off(lane, 1)};
+}
+
+// partial block of unit u: C rows (n) 4 (l >> 4) + e, column (k) l & 15 of each 16 x 16 tile;
+// finish(value, i, j, e) is the stored element
+template <typename F>
+__device__ __forceinline__ void store_block(const Args &a, const Unit &t, const TileLane &tl, const BlockAcc &acc,
+                                            F finish) {
+    float *out = a.partial + (int64_t)t.u * H * H + (int64_t)(t.nb * BM + tl.n0) * H + t.kb * BM + tl.k0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                out[(int64_t)(16 * i + 4 * tl.g + e) * H + 16 * j + tl.li] = finish(acc[i][j][e], i, j, e);
 }
 
 __global__ __launch_bounds__(NTHR, 1) void k_wgrad(Args a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    // blockIdx -> (unit = (job, chunk), block of 4); the 4 blocks of a unit share an XCD
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int b4 = local & 3;
-    const int u = 8 * (local >> 2) + xcd;
-    if (u >= a.n_units) return;   // whole workgroup: uniform
-    const int job = u / a.chunks, chunk = u % a.chunks;
-    const int nb = b4 & 1, kb = b4 >> 1;
-    const int64_t p0 = (int64_t)chunk * a.chunk_points;
-    const int64_t p1 = p0 + a.chunk_points < a.n_points ? p0 + a.chunk_points : a.n_points;
+    Unit U;
+    if (!unit_of(a, U)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    // staging role: point r of the step, columns 8j .. 8j+7 and 128+8j .. 128+8j+7 (j = t & 15)
-    const int r = tid >> 4, jc = tid & 15;
-    const float *dsrc = a.dy[job] + nb * BM + 8 * jc;
-    const float *xsrc = a.x[job] + kb * BM + 8 * jc;
-    const int woff = PITCH * prow(r) + 16 * jc;   // + 256 for the second 8 columns
-    f4 sd[4], sx[4];
-    bool ok = true;   // the staged row is a point of the chunk (else it is staged as zeros)
-    // The zeroing of a row past the chunk happens in put(), not here: a select right after
-    // the loads made the compiler wait for them (s_waitcnt vmcnt(0)) before the step's MFMAs,
+    const Stage S = stage_of(a, U, tid);
+    f4 sd[4], sx[4];   // the staged row (load_row)
+    bool ok = true;    // it is a point of the chunk (else it is staged as zeros)
+    // The zeroing of a row past the chunk happens in put(), not after the loads: a select right
+    // after them made the compiler wait for them (s_waitcnt vmcnt(0)) before the step's MFMAs,
     // exposing a full L2 / HBM latency per 32-point step on every wave.
-    auto load = [&](int64_t pbase) {
-        const int64_t p = pbase + r;
-        ok = p < p1;
-        const int64_t pc = ok ? p : 0;   // in-bounds address (row 0)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int col = 128 * (i >> 1) + 4 * (i & 1);
-            sd[i] = *reinterpret_cast<const f4 *>(dsrc + pc * H + col);
-            sx[i] = *reinterpret_cast<const f4 *>(xsrc + pc * H + col);
-        }
-    };
     // 16 floats -> 3 parts x 2 chunks of 8 bf16 at (row pi(r), bytes 16 jc and 256 + 16 jc)
     auto put = [&](char *img0, const f4 (&v)[4]) {
 #pragma unroll
@@ -138,7 +201,7 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad(Args a) {
                 split_pair(x0, x1, e0, e1, e2);
                 q0[j] = e0; q1[j] = e1; q2[j] = e2;
             }
-            char *d = img0 + woff + 256 * h;
+            char *d = img0 + S.woff + 256 * h;
             *reinterpret_cast<u4 *>(d) = q0;
             *reinterpret_cast<u4 *>(d + IMG_BYTES) = q1;
             *reinterpret_cast<u4 *>(d + 2 * IMG_BYTES) = q2;
@@ -146,35 +209,31 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad(Args a) {
     };
     char *imd = lds, *imx = lds + 3 * IMG_BYTES;
 
-    f4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const int n0 = 128 * (wave & 1), k0 = 64 * (wave >> 1);
-    // this lane's transpose-read offsets (points 8g + q and 8g + 4 + q, column pair pp)
-    const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-    const int t_lo = PITCH * prow(8 * g + q) + 8 * pp, t_hi = PITCH * prow(8 * g + 4 + q) + 8 * pp;
-    const char *ad = imd + 2 * n0, *ax = imx + 2 * k0;
+    BlockAcc acc;
+    acc_zero(acc);
+    const TileLane T = tile_lane(wave, lane);
+    const int t_lo = T.t_lo, t_hi = T.t_hi;
+    const char *ad = imd + 2 * T.n0, *ax = imx + 2 * T.k0;
+    const int64_t p0 = U.p0, p1 = U.p1;
 
-    load(p0);
+    ok = load_row(S, p0 + S.r, p1, sd, sx);
 #pragma unroll 1
     for (int64_t pb = p0; pb < p1; pb += PS) {
         __syncthreads();   // the previous step's fragment reads are done
         put(imd, sd);
         put(imx, sx);
         __syncthreads();
-        if (pb + PS < p1) load(pb + PS);   // in flight during this step's MFMAs
+        if (pb + PS < p1) ok = load_row(S, pb + PS + S.r, p1, sd, sx);   // in flight during this step's MFMAs
         bf8 xb[4][3];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int pt = 0; pt < 3; ++pt) xb[j][pt] = tr_frag(ax + pt * IMG_BYTES + 32 * j, t_lo, t_hi);
+            for (int pt = 0; pt < 3; ++pt) xb[j][pt] = tr_frag<bf8>(ax + pt * IMG_BYTES + 32 * j, t_lo, t_hi);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             bf8 da[3];
 #pragma unroll
-            for (int pt = 0; pt < 3; ++pt) da[pt] = tr_frag(ad + pt * IMG_BYTES + 32 * i, t_lo, t_hi);
+            for (int pt = 0; pt < 3; ++pt) da[pt] = tr_frag<bf8>(ad + pt * IMG_BYTES + 32 * i, t_lo, t_hi);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 f4 v = acc[i][j];
@@ -188,14 +247,7 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad(Args a) {
             }
         }
     }
-    // partial block: C rows (n) 4 (l >> 4) + e, column (k) l & 15 of each 16 x 16 tile
-    float *out = a.partial + (int64_t)u * H * H + (int64_t)(nb * BM + n0) * H + kb * BM + k0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[(int64_t)(16 * i + 4 * g + e) * H + 16 * j + li] = acc[i][j][e];
+    store_block(a, U, T, acc, [](float v, int, int, int) { return v; });
 }
 
 // ---- f16x3, double-buffered (k_wgrad_h) --------------------------------------------------
@@ -214,12 +266,22 @@ constexpr int INIT_STEPS = 4;                       // steps whose maxima set th
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ h8 tr_frag_h(const char *base, int lo, int hi) {
-    const s4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(base + lo));
-    const s4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(base + hi));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    const s8 v = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return __builtin_bit_cast(h8, v);
+// v0 s0, v1 s1 (8 channels of one point row, scaled) -> two fp16 parts: hi at d, lo at
+// d + IMG_BYTES.  Returns the maximum of m and every |split value|.
+__device__ __forceinline__ float split_store8(const f4 &v0, const f4 &v1, const f4 &s0, const f4 &s1, char *d,
+                                              float m = 0.f) {
+    const f4 y0 = v0 * s0, y1 = v1 * s1;
+    u4 hi, lo;
+    const f2 q[4] = {f2{y0.x, y0.y}, f2{y0.z, y0.w}, f2{y1.x, y1.y}, f2{y1.z, y1.w}};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        hi[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(q[e], h2));
+        lo[e] = resid_pk(hi[e], q[e].x, q[e].y);
+        m = fmaxf(m, fmaxf(fabsf(q[e].x), fabsf(q[e].y)));
+    }
+    *reinterpret_cast<u4 *>(d) = hi;
+    *reinterpret_cast<u4 *>(d + IMG_BYTES) = lo;
+    return m;
 }
 
 #ifdef PNR_WGH_STATS   // diagnostic: [0] retunes after step 0, [1] steps, [2] workgroups, channel scale moves
@@ -235,69 +297,31 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
     unsigned *chmax = reinterpret_cast<unsigned *>(lds + HS_MAX);
     int *flag = reinterpret_cast<int *>(lds + HS_FLAG);
     unsigned *tmax = reinterpret_cast<unsigned *>(lds + HS_FLAG + 8);   // dY, X maxima of a retune
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int b4 = local & 3;
-    const int u = 8 * (local >> 2) + xcd;
-    if (u >= a.n_units) return;   // whole workgroup: uniform
-    const int job = u / a.chunks, chunk = u % a.chunks;
-    const int nb = b4 & 1, kb = b4 >> 1;
-    const int64_t p0 = (int64_t)chunk * a.chunk_points;
-    const int64_t p1 = p0 + a.chunk_points < a.n_points ? p0 + a.chunk_points : a.n_points;
+    Unit U;
+    if (!unit_of(a, U)) return;
+    const int64_t p0 = U.p0, p1 = U.p1;
     const int nsteps = p1 > p0 ? (int)((p1 - p0 + PS - 1) / PS) : 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    // staging role: point r of the step, columns 8j .. 8j+7 and 128+8j .. 128+8j+7 (j = t & 15)
-    const int r = tid >> 4, jc = tid & 15;
-    const float *dsrc = a.dy[job] + nb * BM + 8 * jc;
-    const float *xsrc = a.x[job] + kb * BM + 8 * jc;
-    const int woff = PITCH * prow(r) + 16 * jc;   // + 256 for the second 8 columns
-    // (slow path) one step's row of this thread: 4 f4 of dY, 4 of X (columns 8 jc + 0..7,
-    // 128 + 8 jc + 0..7); ok = the row is a point of the chunk
-    auto load = [&](int step, f4 (&d)[4], f4 (&x)[4], bool &ok) {
-        const int64_t p = p0 + (int64_t)step * PS + r;
-        ok = p < p1;
-        const int64_t pc = ok ? p : 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int col = 128 * (i >> 1) + 4 * (i & 1);
-            d[i] = *reinterpret_cast<const f4 *>(dsrc + pc * H + col);
-            x[i] = *reinterpret_cast<const f4 *>(xsrc + pc * H + col);
-        }
-    };
+    const Stage S = stage_of(a, U, tid);
+    const int r = S.r, jc = S.jc, woff = S.woff;
     // (slow path) v 2^-E -> two fp16 parts of 8 channels x 2 at (row pi(r), bytes 16 jc and
     // 256 + 16 jc) of the image pair at img (hi) / img + IMG_BYTES (lo); a row past the chunk
     // (!ok) is staged as zeros
     auto put = [&](char *img, const float *scb, const f4 (&v)[4], bool ok) {
+        const f4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const f4 s0 = *reinterpret_cast<const f4 *>(scb + 128 * h + 8 * jc);
-            const f4 s1 = *reinterpret_cast<const f4 *>(scb + 128 * h + 8 * jc + 4);
-            const f4 z = {0.f, 0.f, 0.f, 0.f};
-            const f4 y0 = (ok ? v[2 * h] : z) * s0, y1 = (ok ? v[2 * h + 1] : z) * s1;
-            u4 hi, lo;
-            const f2 q[4] = {f2{y0.x, y0.y}, f2{y0.z, y0.w}, f2{y1.x, y1.y}, f2{y1.z, y1.w}};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                hi[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(q[k], h2));
-                lo[k] = resid_pk(hi[k], q[k].x, q[k].y);
-            }
-            char *d = img + woff + 256 * h;
-            *reinterpret_cast<u4 *>(d) = hi;
-            *reinterpret_cast<u4 *>(d + IMG_BYTES) = lo;
+            const float *sh = scb + 128 * h + 8 * jc;
+            split_store8(ok ? v[2 * h] : z, ok ? v[2 * h + 1] : z, *reinterpret_cast<const f4 *>(sh),
+                         *reinterpret_cast<const f4 *>(sh + 4), img + woff + 256 * h);
         }
     };
 
-    f4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const int n0 = 128 * (wave & 1), k0 = 64 * (wave >> 1);
-    // this lane's transpose-read offsets (points 8g + q and 8g + 4 + q, column pair pp)
-    const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-    const int t_lo = PITCH * prow(8 * g + q) + 8 * pp, t_hi = PITCH * prow(8 * g + 4 + q) + 8 * pp;
+    BlockAcc acc;
+    acc_zero(acc);
+    const TileLane T = tile_lane(wave, lane);
+    const int n0 = T.n0, k0 = T.k0, g = T.g, li = T.li, t_lo = T.t_lo, t_hi = T.t_hi;
 
     // the slow path: re-read step `step`, move the scales of its overflowing channels, rescale the
     // accumulators and split the step again into image set `set`
@@ -324,10 +348,10 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
         };
         // the maxima of steps step + 1 .. step + scan - 1 too (the chunk's first scales)
         for (int q = 1; q < scan; ++q) {
-            load(step + q, td, tx, tok);
+            tok = load_row(S, p0 + (int64_t)(step + q) * PS + r, p1, td, tx);
             note();
         }
-        load(step, td, tx, tok);
+        tok = load_row(S, p0 + (int64_t)step * PS + r, p1, td, tx);
         note();
         __syncthreads();
         {   // channel tid
@@ -388,7 +412,7 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
     auto load_piece = [&](int step, int k) {
         const int64_t p = p0 + (int64_t)step * PS + r;
         const int64_t pc = p < p1 ? p : 0;   // rows past the chunk: a valid row, zeroed by okf
-        const float *src = ((k >> 1) ? xsrc : dsrc) + pc * H + 128 * (k & 1);
+        const float *src = ((k >> 1) ? S.xsrc : S.dsrc) + pc * H + 128 * (k & 1);
         stg[k][0] = *reinterpret_cast<const f4 *>(src);
         stg[k][1] = *reinterpret_cast<const f4 *>(src + 4);
     };
@@ -402,19 +426,9 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
         float m = 0.f;   // max |split value| of step s + 1 (a last step's split is never read)
         auto put_piece = [&](int k) {
             const float *scb = sc + 256 * (k >> 1) + 128 * (k & 1) + 8 * jc;
-            const f4 y0 = stg[k][0] * (*reinterpret_cast<const f4 *>(scb) * okf);
-            const f4 y1 = stg[k][1] * (*reinterpret_cast<const f4 *>(scb + 4) * okf);
-            u4 hi, lo;
-            const f2 q[4] = {f2{y0.x, y0.y}, f2{y0.z, y0.w}, f2{y1.x, y1.y}, f2{y1.z, y1.w}};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                hi[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(q[e], h2));
-                lo[e] = resid_pk(hi[e], q[e].x, q[e].y);
-                m = fmaxf(m, fmaxf(fabsf(q[e].x), fabsf(q[e].y)));
-            }
-            char *d = nxt + 2 * IMG_BYTES * (k >> 1) + woff + 256 * (k & 1);
-            *reinterpret_cast<u4 *>(d) = hi;
-            *reinterpret_cast<u4 *>(d + IMG_BYTES) = lo;
+            m = split_store8(stg[k][0], stg[k][1], *reinterpret_cast<const f4 *>(scb) * okf,
+                             *reinterpret_cast<const f4 *>(scb + 4) * okf,
+                             nxt + 2 * IMG_BYTES * (k >> 1) + woff + 256 * (k & 1), m);
             load_piece(s + 2, k);
         };
         const char *ad = cur + 2 * n0, *ax = cur + 2 * IMG_BYTES + 2 * k0;
@@ -422,15 +436,15 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt) xb[j][pt] = tr_frag_h(ax + pt * IMG_BYTES + 32 * j, t_lo, t_hi);
+            for (int pt = 0; pt < 2; ++pt) xb[j][pt] = tr_frag<h8>(ax + pt * IMG_BYTES + 32 * j, t_lo, t_hi);
         // dY fragments one row tile ahead: tile i + 1's reads are in flight during tile i's MFMAs
-        h8 dh = tr_frag_h(ad, t_lo, t_hi), dl = tr_frag_h(ad + IMG_BYTES, t_lo, t_hi);
+        h8 dh = tr_frag<h8>(ad, t_lo, t_hi), dl = tr_frag<h8>(ad + IMG_BYTES, t_lo, t_hi);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             h8 nh = dh, nl = dl;
             if (i < 7) {
-                nh = tr_frag_h(ad + 32 * (i + 1), t_lo, t_hi);
-                nl = tr_frag_h(ad + IMG_BYTES + 32 * (i + 1), t_lo, t_hi);
+                nh = tr_frag<h8>(ad + 32 * (i + 1), t_lo, t_hi);
+                nl = tr_frag<h8>(ad + IMG_BYTES + 32 * (i + 1), t_lo, t_hi);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -459,18 +473,10 @@ __global__ __launch_bounds__(NTHR, 1) void k_wgrad_h(Args a) {
         atomicAdd(&g_wgh_stats[2], 1ull);
     }
 #endif
-    // partial block G = acc 2^(E_row + E_col): C rows (n) 4 (l >> 4) + e, column (k) l & 15
-    float *out = a.partial + (int64_t)u * H * H + (int64_t)(nb * BM + n0) * H + kb * BM + k0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ec = Ee[256 + k0 + 16 * j + li];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                out[(int64_t)(16 * i + 4 * g + e) * H + 16 * j + li] =
-                    __builtin_ldexpf(acc[i][j][e], Ee[n0 + 16 * i + 4 * g + e] + ec);
-    }
+    // partial block G = acc 2^(E_row + E_col)
+    store_block(a, U, T, acc, [&](float v, int i, int j, int e) {
+        return __builtin_ldexpf(v, Ee[n0 + 16 * i + 4 * g + e] + Ee[256 + k0 + 16 * j + li]);
+    });
 }
 
 // G_j = sum over chunks (in chunk order) of the partials; one thread per 4 outputs
@@ -518,7 +524,7 @@ size_t wgrad_workspace_bytes(int n_jobs, int64_t n_points) {
 }
 
 int launch_wgrad(const float *const *dy, const float *const *x, float *const *g, int n_jobs, int64_t n_points,
-                 void *ws, size_t ws_bytes, hipStream_t st, int arith) {
+                 void *ws, size_t ws_bytes, int arith, hipStream_t st) {
     if (arith != PNR_WGRAD_F16X3 && arith != PNR_WGRAD_BF16X6)
         return fail(PNR_ERR_INVALID, "weight grad: arithmetic %d is not PNR_WGRAD_F16X3 / PNR_WGRAD_BF16X6", arith);
     if (n_jobs < 1 || n_jobs > wg::MAX_JOBS) return fail(PNR_ERR_UNSUPPORTED, "weight grad: 1..16 layers");
@@ -535,8 +541,7 @@ int launch_wgrad(const float *const *dy, const float *const *x, float *const *g,
     wg::Outs o = {};
     for (int j = 0; j < n_jobs; ++j) {
         if (!dy[j] || !x[j] || !g[j]) return fail(PNR_ERR_INVALID, "weight grad: NULL matrix (layer %d)", j);
-        if (((reinterpret_cast<uintptr_t>(dy[j]) | reinterpret_cast<uintptr_t>(x[j]) |
-              reinterpret_cast<uintptr_t>(g[j])) & 15) != 0)
+        if (misaligned(15, dy[j], x[j], g[j]))
             return fail(PNR_ERR_INVALID, "weight grad: matrices must be 16-byte aligned");
         a.dy[j] = dy[j];
         a.x[j] = x[j];
@@ -548,12 +553,12 @@ int launch_wgrad(const float *const *dy, const float *const *x, float *const *g,
     a.n_points = n_points;
     a.chunk_points = ((n_points + a.chunks - 1) / a.chunks + wg::PS - 1) / wg::PS * wg::PS;
     a.partial = static_cast<float *>(ws);
-    const int unit_groups = (a.n_units + 7) / 8;   // units padded to a multiple of 8 (one per XCD)
+    // units padded to a multiple of 8 (one per XCD), 4 workgroups each
+    const dim3 grid((unsigned)((a.n_units + 7) / 8 * 8 * 4));
     if (arith == PNR_WGRAD_BF16X6)
-        hipLaunchKernelGGL(wg::k_wgrad, dim3((unsigned)(unit_groups * 8 * 4)), dim3(wg::NTHR), wg::LDS_BYTES, st, a);
+        hipLaunchKernelGGL(wg::k_wgrad, grid, dim3(wg::NTHR), wg::LDS_BYTES, st, a);
     else
-        hipLaunchKernelGGL(wg::k_wgrad_h, dim3((unsigned)(unit_groups * 8 * 4)), dim3(wg::NTHR), wg::LDS_BYTES_H, st,
-                           a);
+        hipLaunchKernelGGL(wg::k_wgrad_h, grid, dim3(wg::NTHR), wg::LDS_BYTES_H, st, a);
     if (!launch_ok("wgrad")) return PNR_ERR_HIP;
     const int64_t nt = (int64_t)n_jobs * (wg::H * wg::H / 4);
     hipLaunchKernelGGL(wg::k_wgrad_reduce, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, o, a.partial,

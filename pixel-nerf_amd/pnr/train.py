@@ -72,13 +72,18 @@ def _on_device(dev, what, *tensors):
             raise ValueError("pnr: %s is on %s, the launch device is %s" % (name, t.device, dev))
 
 
+def _stages(mlp, ns):
+    """(block count, blocks run once per view row: all with one view, else those before combine_layer, lin_z)."""
+    nb = mlp.n_blocks
+    return nb, (min(mlp.combine_layer, nb) if ns > 1 else nb), list(getattr(mlp, "lin_z", []))
+
+
 def forward_flop(mlp, P, ns=1):
     """Algorithmic FLOP of the ResnetFC forward over P points with ns source views (the reference's
     per-point arithmetic, resnetfc.py:132-184: lin_in, lin_z and both block layers before
     combine_layer once per view, the rest once per point, lin_out)."""
-    nb = mlp.n_blocks
-    nc = min(mlp.combine_layer, nb) if ns > 1 else nb
-    nz = len(getattr(mlp, "lin_z", []))
+    nb, nc, lin_z = _stages(mlp, ns)
+    nz = len(lin_z)
     H, d_in = 512, mlp.lin_in.weight.shape[1]
     per_view = 2 * H * d_in + 2 * H * H * (nz + 2 * nc)
     per_point = 2 * H * H * 2 * (nb - nc) + 2 * 4 * H
@@ -88,9 +93,8 @@ def forward_flop(mlp, P, ns=1):
 def backward_chain_flop(mlp, P, ns=1):
     """Algorithmic FLOP of k_mlp_bwd's input-gradient chain: W^T dY of every 512-wide layer (the
     blocks before combine_layer once per view) and d_o W_out; lin_in's d_feat is a torch GEMM."""
-    nb = mlp.n_blocks
-    nc = min(mlp.combine_layer, nb) if ns > 1 else nb
-    nz = len(getattr(mlp, "lin_z", []))
+    nb, nc, lin_z = _stages(mlp, ns)
+    nz = len(lin_z)
     H = 512
     return float(P) * (ns * 2 * H * H * (nz + 2 * nc) + 2 * H * H * 2 * (nb - nc) + 2 * 4 * H)
 
@@ -111,26 +115,25 @@ def _save_views(save, P, n_blocks, H=512, ns=1):
     return feat, z, slot
 
 
-def mlp_backward(mlp, save, d_o, P, ns=1, use_wgrad=False):
+def _lin_in_backward(mlp, g, dx, feat, d_bias):
+    """lin_in's gradients into ``g`` from its output gradient ``dx`` (R, 512); returns d_feat (R, 64)."""
+    d_in = mlp.lin_in.weight.shape[1]
+    g[mlp.lin_in.weight] = _tall_mm(dx, feat)[:, :d_in]
+    g[mlp.lin_in.bias] = d_bias
+    d_feat = torch.zeros(dx.shape[0], 64, device=dx.device, dtype=torch.float32)
+    d_feat[:, :d_in] = dx @ mlp.lin_in.weight.detach()
+    return d_feat
+
+
+def mlp_backward(mlp, save, d_o, P, ns=1):
     """ResnetFC backward (resnetfc.py:132-184) given dL/d(pre-head output) ``d_o`` (P, 4),
-    for ``ns`` source views per point.  Returns ({param: grad}, d_feat (ns P, 64),
-    d_zlat (ns P, 512) or None), rows view-major like the activation save.
+    for ``ns`` source views per point, in plain torch: the fp32 / bf16 models' backward and the
+    reference of the fused one.  Returns ({param: grad}, d_feat (ns P, 64), d_zlat (ns P, 512) or
+    None), rows view-major like the activation save.
     The 512-wide GEMMs are fp32 hipBLASLt GEMMs (split-fp16 GEMMs assembled from torch
-    ops measured 2x slower end to end: the split / scale passes cost more than they save);
-    with ``use_wgrad`` the 512 x 512 weight gradients are ``pnr_weight_grad`` launches
-    instead (one per row count: ns P rows before combine_layer, P after)."""
+    ops measured 2x slower end to end: the split / scale passes cost more than they save)."""
     mm = torch.mm
-    jobs = {}   # rows -> [(param, dY, X)] for pnr_weight_grad
-
-    def wgrad(param, dy, x):
-        if use_wgrad:
-            jobs.setdefault(dy.shape[0], []).append((param, dy, x))
-        else:
-            g[param] = mm(dy.t(), x)
-
-    nb = mlp.n_blocks
-    nc = min(mlp.combine_layer, nb) if ns > 1 else nb
-    lin_z = list(getattr(mlp, "lin_z", []))
+    nb, nc, lin_z = _stages(mlp, ns)
     feat, z, slot = _save_views(save, P, nb, ns=ns)
     g = {}
     xf = slot(2 * nb, P)
@@ -144,15 +147,15 @@ def mlp_backward(mlp, save, d_o, P, ns=1, use_wgrad=False):
         rows = ns * P if b < nc else P
         hb, xb = slot(nb + b, rows), slot(b, rows)
         w1, w0 = blk.fc_1.weight.detach(), blk.fc_0.weight.detach()
-        wgrad(blk.fc_1.weight, dx, hb)
+        g[blk.fc_1.weight] = mm(dx.t(), hb)
         g[blk.fc_1.bias] = dx.sum(0)
         dh = mm(dx, w1) * (hb > 0)
-        wgrad(blk.fc_0.weight, dh, xb)
+        g[blk.fc_0.weight] = mm(dh.t(), xb)
         g[blk.fc_0.bias] = dh.sum(0)
         dx = dx + mm(dh, w0) * (xb > 0)
         if b < len(lin_z):
             lz = lin_z[b]
-            wgrad(lz.weight, dx, z)
+            g[lz.weight] = mm(dx.t(), z)
             g[lz.bias] = dx.sum(0)
             t = mm(dx, lz.weight.detach())
             dz = t if dz is None else dz + t
@@ -160,18 +163,7 @@ def mlp_backward(mlp, save, d_o, P, ns=1, use_wgrad=False):
             # x = mean over views at the start of block nc (combine_interleaved): every view's
             # row gets dL/d(mean) / ns, rows view-major
             dx = (dx / ns).repeat(ns, 1)
-    d_in = mlp.lin_in.weight.shape[1]
-    g[mlp.lin_in.weight] = _tall_mm(dx, feat)[:, :d_in]
-    g[mlp.lin_in.bias] = dx.sum(0)
-    d_feat = torch.zeros(ns * P, 64, device=dx.device, dtype=torch.float32)
-    d_feat[:, :d_in] = dx @ mlp.lin_in.weight.detach()
-    for rows, js in jobs.items():
-        for i in range(0, len(js), 16):   # pnr_weight_grad: up to 16 layers per launch
-            part = js[i:i + 16]
-            gw = weight_grad([dy.contiguous() for _, dy, _ in part], [x for _, _, x in part], rows)
-            for j, (param, _, _) in enumerate(part):
-                g[param] = gw[j]
-    return g, d_feat, dz
+    return g, _lin_in_backward(mlp, g, dx, feat, dx.sum(0)), dz
 
 
 def weight_grad(dys, xs, P, arith="f16x3"):
@@ -232,9 +224,7 @@ def mlp_backward_fused(mlp, code, precision, save, d_o, P, ns=1, wgrad_arith="f1
     (fp16 split products, fp32-level), one per row count (ns P view rows before combine_layer, P
     after), over its per-layer output gradients and the activation save."""
     desc, packed, packed_t = mlp.packed_t(code, precision)
-    nb = mlp.n_blocks
-    nc = min(mlp.combine_layer, nb) if ns > 1 else nb
-    lin_z = list(getattr(mlp, "lin_z", []))
+    nb, nc, lin_z = _stages(mlp, ns)
     R = ns * P
     feat, z, slot = _save_views(save, P, nb, ns=ns)
     dev = d_o.device
@@ -258,33 +248,29 @@ def mlp_backward_fused(mlp, code, precision, save, d_o, P, ns=1, wgrad_arith="f1
     g[mlp.lin_out.weight] = _tall_mm(d_o, xf)
     g[mlp.lin_out.bias] = d_o.sum(0)
     # weight gradients grouped by row count: fc_0 (dY^T relu(x_b)), fc_1 (dY^T relu(h_b)),
-    # lin_z (dY^T z)
+    # lin_z (dY^T z); the bias gradients are the kernel's column sums
     jobs = {}
     for b, blk in enumerate(mlp.blocks):
         rows = R if b < nc else P
         jobs.setdefault(rows, []).extend([(blk.fc_0.weight, dy[b, :rows], slot(b, rows)),
                                           (blk.fc_1.weight, dy[nb + 1 + b, :rows], slot(nb + b, rows))])
+        g[blk.fc_0.bias], g[blk.fc_1.bias] = sums[b], sums[nb + 1 + b]
     for b, lz in enumerate(lin_z):
         rows = R if b < nc else P
         jobs.setdefault(rows, []).append((lz.weight, dy[nb + b, :rows], z[:rows]))
+        g[lz.bias] = sums[nb + b]
     for rows, js in jobs.items():
         for i in range(0, len(js), 16):   # pnr_weight_grad: up to 16 layers per launch
             part = js[i:i + 16]
             gw = weight_grad([d for _, d, _ in part], [x for _, _, x in part], rows, wgrad_arith)
             for j, (param, _, _) in enumerate(part):
                 g[param] = gw[j]
-    for b, blk in enumerate(mlp.blocks):
-        g[blk.fc_0.bias] = sums[b]
-        g[blk.fc_1.bias] = sums[nb + 1 + b]
-    for b, lz in enumerate(lin_z):
-        g[lz.bias] = sums[nb + b]
-    dx = dy[nb]
-    d_in = mlp.lin_in.weight.shape[1]
-    g[mlp.lin_in.weight] = _tall_mm(dx, feat)[:, :d_in]
-    g[mlp.lin_in.bias] = sums[nb]
-    d_feat = torch.zeros(R, 64, device=dev, dtype=torch.float32)
-    d_feat[:, :d_in] = dx @ mlp.lin_in.weight.detach()
-    return g, d_feat, dzl
+    return g, _lin_in_backward(mlp, g, dy[nb], feat, sums[nb]), dzl
+
+
+def _rays_of(net, rays, B):
+    """The pnr_rays of a (B, 8) ray batch split evenly over the net's objects."""
+    return _lib.Rays(_lib.ptr(rays), B, B // net.num_objs)
 
 
 class FinePass:
@@ -330,9 +316,8 @@ class RenderPoints(torch.autograd.Function):
         ws_bytes = lib.pnr_point_query_workspace_bytes(sc, P)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
         out = torch.empty(P, 4, dtype=torch.float32, device=dev)
-        r = _lib.Rays(_lib.ptr(rays), B, B // net.num_objs)
         e0 = _ev_begin()
-        _lib.check(lib.pnr_render_points(sc, desc, _lib.ptr(packed), r, _lib.ptr(z), K, _lib.ptr(out),
+        _lib.check(lib.pnr_render_points(sc, desc, _lib.ptr(packed), _rays_of(net, rays, B), _lib.ptr(z), K, _lib.ptr(out),
                                          _lib.ptr(save), _lib.ptr(ws), ws_bytes, _lib.stream_of(dev)),
                    "pnr_render_points")
         _ev_end("forward", e0, forward_flop(mlp, P, ns))
@@ -356,7 +341,7 @@ class RenderPoints(torch.autograd.Function):
             g, d_feat, d_zlat = mlp_backward_fused(mlp, net.code, net.mlp_precision, save, d_o, P, ns,
                                                    getattr(net, "wgrad_arith", "f16x3"))
         else:
-            g, d_feat, d_zlat = mlp_backward(mlp, save, d_o, P, ns, use_wgrad=net.mlp_precision == "f16x3")
+            g, d_feat, d_zlat = mlp_backward(mlp, save, d_o, P, ns)
         need_z, need_lat = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         d_z = torch.empty(P, dtype=torch.float32, device=z.device) if need_z else None
         d_lat = torch.zeros_like(latent_cl) if need_lat else None
@@ -366,12 +351,12 @@ class RenderPoints(torch.autograd.Function):
             lib = _lib.load()
             _on_device(z.device, "packed rays d_feat d_zlat d_latent cams latent", ctx.packed, rays, d_feat,
                        d_zlat, d_lat, net.cams, net.encoder.latent_cl)
-            r = _lib.Rays(_lib.ptr(rays), B, B // net.num_objs)
             zm = getattr(ctx, "z_mask", None)
             if zm is not None:
                 zm = zm.reshape(P).to(device=z.device, dtype=torch.uint8).contiguous()
             _lib.check(lib.pnr_points_input_backward_masked(
-                net.hip_scene(), ctx.desc, _lib.ptr(ctx.packed), r, _lib.ptr(z), K, _lib.ptr(d_feat.contiguous()),
+                net.hip_scene(), ctx.desc, _lib.ptr(ctx.packed), _rays_of(net, rays, B), _lib.ptr(z), K,
+                _lib.ptr(d_feat.contiguous()),
                 _lib.ptr(d_zlat.contiguous()), _lib.ptr(d_lat), _lib.ptr(d_z), _lib.ptr(zm) if need_z else None,
                 _lib.stream_of(z.device)), "pnr_points_input_backward_masked")
         grads = [g.get(p) for p in ctx.params]

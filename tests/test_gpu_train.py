@@ -619,6 +619,107 @@ def test_weight_grad_arith_selects_kernel():
     assert rc == -1 and b"arithmetic" in lib.pnr_last_error()
 
 
+def test_abi_forwarding_wrappers_match_full_calls():
+    """The ABI's forwarding wrappers give the bits of the calls they forward to: pnr_mlp_backward,
+    pnr_mlp_backward_bias and pnr_mlp_backward_views(n_views = 1) on dy / d_zlat (and the latter two
+    on d_bias), pnr_weight_grad and pnr_weight_grad_arith(PNR_WGRAD_F16X3), and
+    pnr_points_input_backward and its _masked form with a NULL mask on d_z (d_latent is summed with
+    float atomics and is not compared).  Two blocks, one lin_z, one view, 2 rays x 41 = 82 points
+    (one full 64-point tile and a ragged one of 18); output buffers are pre-filled with a fixed
+    pattern, so rows no call may write are compared too."""
+    import ctypes
+    from types import SimpleNamespace
+
+    from pnr import _lib, train
+
+    K, nb = 41, 2
+    cs = case(sb=2, rays_per_obj=1, kc=K, combine_layer=1, n_blocks=nb)
+    net = PixelNeRFNet(conf(1, nb))
+    net.load_state_dict(cs["sd"], strict=False)
+    net = net.to(DEV)
+    net.mlp_precision = "f16x3"
+    net.encode_latent(cs["latent"].to(DEV), cs["poses"].to(DEV), cs["focal"].to(DEV),
+                      (cs["width"], cs["height"]), c=cs["c"].to(DEV), num_objs=2)
+    mlp = net.mlp_coarse
+    assert len(mlp.lin_z) == 1
+    rays = cs["rays"].to(DEV).reshape(-1, 8).contiguous()
+    t = torch.linspace(0.0, 1.0, K, device=DEV)
+    z = (rays[:, 6:7] + (rays[:, 7:8] - rays[:, 6:7]) * t).contiguous()
+    ctx = SimpleNamespace()
+    ctx.save_for_backward = lambda *ts: setattr(ctx, "saved", ts)
+    with torch.no_grad():
+        train.RenderPoints.forward(ctx, net, True, rays, z, net.encoder.latent_cl, *train.mlp_params(mlp))
+    save = ctx.saved[3]
+    P = rays.shape[0] * K
+    assert P == 82
+    gen = torch.Generator(device="cpu").manual_seed(7)
+    d_o = (torch.randn(P, 4, generator=gen) * 1e-2).to(DEV)
+    desc, packed, packed_t = mlp.packed_t(net.code, "f16x3")
+    w_out = mlp.lin_out.weight.detach().float().contiguous()
+    lib = _lib.load()
+    st = _lib.stream_of(rays.device)
+    wsb = lib.pnr_mlp_backward_workspace_bytes(desc, P)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=DEV)
+
+    def chain(name):
+        dy = torch.full((2 * nb + 1, P, 512), -7.0, device=DEV)
+        dzl = torch.full((P, 512), -7.0, device=DEV)
+        sums = torch.full((2 * nb + 1, 512), -7.0, device=DEV)
+        head = (desc, _lib.ptr(packed), _lib.ptr(packed_t), _lib.ptr(w_out), _lib.ptr(save), _lib.ptr(d_o), P)
+        if name == "pnr_mlp_backward":
+            rc = lib.pnr_mlp_backward(*head, _lib.ptr(dy), _lib.ptr(dzl), st)
+        elif name == "pnr_mlp_backward_bias":
+            rc = lib.pnr_mlp_backward_bias(*head, _lib.ptr(dy), _lib.ptr(dzl), _lib.ptr(sums), _lib.ptr(ws), wsb, st)
+        else:
+            rc = lib.pnr_mlp_backward_views(*head, 1, _lib.ptr(dy), _lib.ptr(dzl), _lib.ptr(sums), _lib.ptr(ws),
+                                            wsb, st)
+        _lib.check(rc, name)
+        torch.cuda.synchronize()
+        return dy, dzl, sums
+
+    plain, bias, views = chain("pnr_mlp_backward"), chain("pnr_mlp_backward_bias"), chain("pnr_mlp_backward_views")
+    assert not torch.equal(views[0], torch.full_like(views[0], -7.0))
+    for got in (plain, bias):
+        assert torch.equal(got[0], views[0]) and torch.equal(got[1], views[1])
+    assert torch.equal(bias[2], views[2])
+    assert torch.equal(plain[2], torch.full_like(plain[2], -7.0))   # no d_bias asked for, none written
+
+    # pnr_weight_grad against pnr_weight_grad_arith(PNR_WGRAD_F16X3): one layer, 33 points
+    Pw = 33
+    d = torch.randn(Pw, 512, generator=gen).to(DEV)
+    x = torch.relu(torch.randn(Pw, 512, generator=gen)).to(DEV)
+    wb = lib.pnr_weight_grad_workspace_bytes(1, Pw)
+    wws = torch.empty(max(wb, 1), dtype=torch.uint8, device=DEV)
+    g0, g1 = torch.full((512, 512), -7.0, device=DEV), torch.full((512, 512), -7.0, device=DEV)
+
+    def arr(v):
+        return (ctypes.c_void_p * 1)(v.data_ptr())
+
+    _lib.check(lib.pnr_weight_grad(arr(d), arr(x), arr(g0), 1, Pw, _lib.ptr(wws), wb, st), "pnr_weight_grad")
+    _lib.check(lib.pnr_weight_grad_arith(arr(d), arr(x), arr(g1), 1, Pw, _lib.WGRAD_ARITH["f16x3"], _lib.ptr(wws),
+                                         wb, st), "pnr_weight_grad_arith")
+    torch.cuda.synchronize()
+    assert torch.equal(g0, g1) and torch.equal(g0, train.weight_grad([d], [x], Pw)[0])
+
+    # pnr_points_input_backward against its _masked form with a NULL mask
+    d_feat = (torch.randn(P, 64, generator=gen) * 1e-2).to(DEV)
+    r = _lib.Rays(_lib.ptr(rays), rays.shape[0], rays.shape[0] // net.num_objs)
+    dzs = []
+    for masked in (False, True):
+        d_lat = torch.zeros_like(net.encoder.latent_cl)
+        d_z = torch.full((P,), -7.0, device=DEV)
+        head = (net.hip_scene(), desc, _lib.ptr(packed), r, _lib.ptr(z), K, _lib.ptr(d_feat), _lib.ptr(views[1]),
+                _lib.ptr(d_lat), _lib.ptr(d_z))
+        if masked:
+            _lib.check(lib.pnr_points_input_backward_masked(*head, None, st), "pnr_points_input_backward_masked")
+        else:
+            _lib.check(lib.pnr_points_input_backward(*head, st), "pnr_points_input_backward")
+        torch.cuda.synchronize()
+        assert torch.isfinite(d_lat).all()
+        dzs.append(d_z)
+    assert torch.equal(dzs[0], dzs[1]) and not bool((dzs[0] == -7.0).any())
+
+
 @pytest.mark.parametrize("coarse", [True, False])
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_grad_point_query_matches_oracle_autograd(precision, coarse):

@@ -9,6 +9,9 @@ in another process, which changes the latent in its last bits.
   python tools/bitwise_ab.py save-all OUT.pt    every k_point_mlp instantiation at the smallest shapes that
                                                 exercise it (cases_all below); per case also the kernel
                                                 family pnr_mlp_last_kernel names
+  python tools/bitwise_ab.py save-train OUT.pt  the training backward through the ABI, into buffers pre-filled with a
+                                                fixed pattern (train_cases below): the fused chain's dy / d_zlat /
+                                                d_bias, the weight gradients in both arithmetics, one training step
   python tools/bitwise_ab.py cmp A.pt B.pt      bitwise equal? (torch.equal per tensor, no tolerance)
   python tools/bitwise_ab.py time OUT.json      HIP-event times of one render of 8,192 rays x (64 + 64)
                                                 per instantiation no bench leg reaches: one warm-up,
@@ -180,6 +183,156 @@ def save_all(out):
     print("saved", out, len(blob), "values", os.environ.get("PNR_LIB_PATH", "default"))
 
 
+# ---- the third case set: the training backward ---------------------------------------------------
+FILL = -7.0   # every output buffer starts as this, so rows a kernel must not write compare too
+
+
+def scale_moves_inputs(case, P=9000):
+    """The (dY, X) of tests/test_gpu_train.py::test_weight_grad_scale_moves[case]."""
+    import torch
+
+    gen = torch.Generator(device="cpu").manual_seed(7)
+    d = torch.randn(P, 512, generator=gen)
+    x = torch.relu(torch.randn(P, 512, generator=gen))
+    if case == "growing":
+        ramp = torch.exp2(torch.linspace(-20, 20, P)).unsqueeze(1)
+        d = d * ramp
+        x = x * ramp.flip(0).sqrt()
+    elif case == "late_channels":
+        d[: P // 2, ::3] = 0.0
+        x[: P // 2, 1::2] = 0.0
+        x[P // 2:, 1::2] *= 1e4
+    elif case == "rays":
+        k = torch.arange(P)
+        u = torch.rand(P // 64 + 1, generator=gen)
+        d = d * torch.exp2(-30.0 * u[k // 64] * (k % 64).float() / 63.0).unsqueeze(1)
+        x = torch.relu(torch.randn(P, 512, generator=gen) - 1.5)
+        x[: P // 3, 5::7] = 0.0
+    elif case == "huge_tiny":
+        d[:, :64] *= 2.0 ** 80
+        d[:, 64:128] *= 2.0 ** -60
+        x[:, :32] *= 2.0 ** -60
+        x[:, 32:64] *= 2.0 ** 20
+    else:
+        d.zero_()
+        x.zero_()
+    return d, x
+
+
+def train_cases():
+    """Yields (name, tensor), every tensor on the CPU."""
+    import ctypes
+    from types import SimpleNamespace
+
+    import torch
+
+    import test_gpu_train as tt
+    from pnr import _lib, train
+    from pnr.models import PixelNeRFNet
+
+    lib = _lib.load()
+    dev = tt.DEV
+
+    def filled(*shape):
+        return torch.full(shape, FILL, dtype=torch.float32, device=dev)
+
+    # (a) pnr_mlp_backward_views on the parameter sets, save and d_o of
+    # test_fused_mlp_backward_matches_torch_backward
+    mark = [m for m in tt.test_fused_mlp_backward_matches_torch_backward.pytestmark if m.name == "parametrize"][0]
+    for ps in mark.args[1]:
+        rays_per_obj, K, ns, comb, nb = ps.values
+        cs = tt.case(sb=2, rays_per_obj=rays_per_obj, kc=K, ns=ns, combine_layer=comb, n_blocks=nb)
+        net = PixelNeRFNet(tt.conf(comb, nb))
+        net.load_state_dict(cs["sd"], strict=False)
+        net = net.to(dev)
+        net.mlp_precision = "f16x3"
+        net.encode_latent(cs["latent"].to(dev), cs["poses"].to(dev), cs["focal"].to(dev),
+                          (cs["width"], cs["height"]), c=cs["c"].to(dev), num_objs=cs["poses"].shape[0])
+        rays = cs["rays"].to(dev).reshape(-1, 8).contiguous()
+        t = torch.linspace(0.0, 1.0, K, device=dev)
+        z = (rays[:, 6:7] + (rays[:, 7:8] - rays[:, 6:7]) * t).contiguous()
+        ctx = SimpleNamespace()
+        ctx.save_for_backward = lambda *ts: setattr(ctx, "saved", ts)
+        mlp = net.mlp_coarse
+        with torch.no_grad():
+            train.RenderPoints.forward(ctx, net, True, rays, z, net.encoder.latent_cl, *train.mlp_params(mlp))
+        save = ctx.saved[3]
+        P = rays.shape[0] * K
+        gen = torch.Generator(device="cpu").manual_seed(7)
+        d_o = (torch.randn(P, 4, generator=gen) * torch.exp2(-20.0 * torch.rand(P, 1, generator=gen))).to(dev)
+        desc, packed, packed_t = mlp.packed_t(net.code, "f16x3")
+        w_out = mlp.lin_out.weight.detach().float().contiguous()
+        dy, sums = filled(2 * nb + 1, ns * P, 512), filled(2 * nb + 1, 512)
+        dzl = filled(ns * P, 512) if len(mlp.lin_z) else None
+        wsb = lib.pnr_mlp_backward_workspace_bytes(desc, P)
+        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+        _lib.check(lib.pnr_mlp_backward_views(desc, _lib.ptr(packed), _lib.ptr(packed_t), _lib.ptr(w_out),
+                                              _lib.ptr(save), _lib.ptr(d_o), P, ns, _lib.ptr(dy), _lib.ptr(dzl),
+                                              _lib.ptr(sums), _lib.ptr(ws), wsb, _lib.stream_of(rays.device)),
+                   "pnr_mlp_backward_views")
+        torch.cuda.synchronize()
+        yield "chain %s | dy" % ps.id, dy.cpu()
+        yield "chain %s | d_bias" % ps.id, sums.cpu()
+        if dzl is not None:
+            yield "chain %s | d_zlat" % ps.id, dzl.cpu()
+        del dy, dzl, save
+
+    # (b) pnr_weight_grad_arith
+    def wgrad(dys, xs, P, arith):
+        n = len(dys)
+        dys, xs = [d.to(dev).contiguous() for d in dys], [x.to(dev).contiguous() for x in xs]
+        out = filled(n, 512, 512)
+        wsb = lib.pnr_weight_grad_workspace_bytes(n, P)
+        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
+        _lib.check(lib.pnr_weight_grad_arith(arr(dys), arr(xs), arr(list(out)), n, P, _lib.WGRAD_ARITH[arith],
+                                             _lib.ptr(ws), wsb, _lib.stream_of(out.device)), "pnr_weight_grad_arith")
+        torch.cuda.synchronize()
+        return out.cpu()
+
+    for n, P in ((3, 1), (3, 33), (3, 4133), (16, 33)):   # test_weight_grad_matches_fp64's data
+        gen = torch.Generator(device="cpu").manual_seed(P + n)
+        dys = [torch.randn(P, 512, generator=gen) * torch.exp2(-30 + 40 * torch.rand(P, 1, generator=gen))
+               for _ in range(n)]
+        xs = [torch.relu(torch.randn(P, 512, generator=gen)) * torch.exp2(-8 * torch.rand(1, 512, generator=gen))
+              for _ in range(n)]
+        for arith in ("f16x3", "bf16x6"):
+            yield "wgrad %d layers P=%d %s" % (n, P, arith), wgrad(dys, xs, P, arith)
+    for case in ("growing", "late_channels", "huge_tiny", "zeros", "rays"):
+        d, x = scale_moves_inputs(case)
+        yield "wgrad scale_moves %s f16x3" % case, wgrad([d], [x], d.shape[0], "f16x3")
+
+    # (c) one training step, the first case of test_training_step_gradients_match_oracle in f16x3: the
+    # MLP parameter gradients and every RenderPoints.backward's d_z (d_latent is summed with atomics)
+    dzs = []
+    orig = train.RenderPoints.backward
+
+    def recording(ctx, d_out):
+        res = orig(ctx, d_out)
+        if res[3] is not None:   # only a pass whose depths carry a gradient (the fine pass's depth samples)
+            dzs.append(res[3].detach().cpu().clone())
+        return res
+
+    train.RenderPoints.backward = staticmethod(recording)
+    try:
+        _, g = tt.hip_grads(tt.case(), "f16x3")
+    finally:
+        train.RenderPoints.backward = staticmethod(orig)
+    for k in sorted(g):
+        if k != "latent":
+            yield "step | %s" % k, g[k]
+    for i, dz in enumerate(dzs):
+        yield "step | d_z of backward %d" % i, dz
+
+
+def save_train(out):
+    import torch
+
+    blob = dict(train_cases())
+    torch.save(blob, out)
+    print("saved", out, len(blob), "values", os.environ.get("PNR_LIB_PATH", "default"))
+
+
 def cmp(a, b):
     import torch
 
@@ -254,4 +407,4 @@ if __name__ == "__main__":
     mode = sys.argv[1]
     if mode == "cmp":
         sys.exit(cmp(sys.argv[2], sys.argv[3]))
-    sys.exit({"save": save, "save-all": save_all, "time": time_cases}[mode](sys.argv[2]))
+    sys.exit({"save": save, "save-all": save_all, "save-train": save_train, "time": time_cases}[mode](sys.argv[2]))
