@@ -472,7 +472,29 @@ int pnr_mlp_pack_t(const pnr_mlp_weights *w, const void *packed, void *packed_t,
  *       [n_blocks + 1 + b] fc_1 of block b; the lin_z of block b takes dy[n_blocks + b];
  *   d_zlat (n_points, 512): dL / d (sampled latent), summed over the lin_z layers
  *       (required when the model has lin_z layers).
- * Weight and bias gradients are then dy^T . (saved layer input) and column sums of dy. */
+ * Weight and bias gradients are then dy^T . (saved layer input) and column sums of dy.
+ *
+ * Accuracy of pnr_mlp_backward* (tests/test_gpu_mlp_bwd_inputs.py holds the kernels to it).  The
+ * chain runs on the forward's f16x3 GEMM with the gradient image scaled by a power of two PER
+ * POINT (per image column: 2^e with max|column| 2^e in (2^13, 2^14], e clamped to [-64, 40]), so
+ * the bound is per point, relative to the point's OWN gradient scale and not to the tensor's:
+ * for a point p and an output T (dy: every slot and view row of p; d_zlat; and d_feat = dy[n_blocks]
+ * W_in computed from it), with s_p(T) = max |exact value| over p's rows of T,
+ *   every row of p is within 2e-5 max(s_p(T), s_clamp(T)) of the exact (fp64) backward of the
+ *   saved activations.
+ * Range: column maxima from 2^-26 (below it the clamp e <= 40, not the data, sets the exponent:
+ * s_clamp(dy) = 2^-26) up to 2^78 (e >= -64 keeps max|column| 2^e <= 2^14; above it the fp16 image
+ * overflows: not supported; tested with d_o up to 2^60).  For d_zlat and d_feat the threshold is
+ * carried through the layer, s_clamp = 2^-26 K A summed over the layers that produce T (K = the
+ * layer's input width, A = the power of two above its largest |weight|, the pack's weight scale).
+ * Below s_clamp the bound is absolute, 2e-5 s_clamp(T) (a clamped column is stored with the fixed
+ * quantum 2^-64; fp32 denormals in d_o are inside this range).
+ * A zero d_o row gives exactly zero rows in dy, d_zlat and d_feat (whole zero tiles included).
+ * A NaN / Inf in d_o row p stays in point p's rows (every view); d_bias sums over the points and
+ * is not confined.  A point's rows do not depend on its position in the launch, on n_points or
+ * on the other points (bit for bit), and a repeated call returns the same bits, d_bias included.
+ * d_bias is the fp32 sum of the returned dy rows: within n_rows 2^-24 sum |dy| per column.
+ * An activation of exactly 0 passes no gradient (the mask bit is [n > 0], torch's relu backward). */
 int pnr_mlp_backward(const pnr_mlp_desc *desc, const void *packed, const void *packed_t,
                      const float *lin_out_w, const float *save, const float *d_o, int64_t n_points,
                      float *dy, float *d_zlat, pnr_stream_t stream);

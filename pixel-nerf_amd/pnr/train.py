@@ -125,11 +125,13 @@ def _lin_in_backward(mlp, g, dx, feat, d_bias):
     return d_feat
 
 
-def mlp_backward(mlp, save, d_o, P, ns=1):
+def mlp_backward(mlp, save, d_o, P, ns=1, dy_slots=None):
     """ResnetFC backward (resnetfc.py:132-184) given dL/d(pre-head output) ``d_o`` (P, 4),
     for ``ns`` source views per point, in plain torch: the fp32 / bf16 models' backward and the
     reference of the fused one.  Returns ({param: grad}, d_feat (ns P, 64), d_zlat (ns P, 512) or
-    None), rows view-major like the activation save.
+    None), rows view-major like the activation save.  ``dy_slots``: None, or a dict that receives
+    every layer's output gradient under pnr_mlp_backward's slot index ([b] fc_0 of block b, [nb]
+    lin_in, [nb + 1 + b] fc_1 of block b), each with the rows its stage has (ns P or P).
     The 512-wide GEMMs are fp32 hipBLASLt GEMMs (split-fp16 GEMMs assembled from torch
     ops measured 2x slower end to end: the split / scale passes cost more than they save)."""
     mm = torch.mm
@@ -142,6 +144,7 @@ def mlp_backward(mlp, save, d_o, P, ns=1):
     g[mlp.lin_out.bias] = d_o.sum(0)
     dx = (d_o @ W) * (xf > 0)
     dz = None
+    dys = {} if dy_slots is None else dy_slots
     for b in reversed(range(nb)):
         blk = mlp.blocks[b]
         rows = ns * P if b < nc else P
@@ -149,7 +152,9 @@ def mlp_backward(mlp, save, d_o, P, ns=1):
         w1, w0 = blk.fc_1.weight.detach(), blk.fc_0.weight.detach()
         g[blk.fc_1.weight] = mm(dx.t(), hb)
         g[blk.fc_1.bias] = dx.sum(0)
+        dys[nb + 1 + b] = dx
         dh = mm(dx, w1) * (hb > 0)
+        dys[b] = dh
         g[blk.fc_0.weight] = mm(dh.t(), xb)
         g[blk.fc_0.bias] = dh.sum(0)
         dx = dx + mm(dh, w0) * (xb > 0)
@@ -163,6 +168,7 @@ def mlp_backward(mlp, save, d_o, P, ns=1):
             # x = mean over views at the start of block nc (combine_interleaved): every view's
             # row gets dL/d(mean) / ns, rows view-major
             dx = (dx / ns).repeat(ns, 1)
+    dys[nb] = dx
     return g, _lin_in_backward(mlp, g, dx, feat, dx.sum(0)), dz
 
 
