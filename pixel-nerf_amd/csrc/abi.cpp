@@ -196,8 +196,10 @@ int pnr_composite_backward(const float *z, const float *raw, const float *rays, 
     if (n_rays == 0) return PNR_OK;
     if (!z || !raw || !rays || !d_rgb || !d_raw) return fail(PNR_ERR_INVALID, "pnr_composite_backward: NULL");
     if (misaligned(15, raw, d_raw)) return fail(PNR_ERR_INVALID, "raw / d_raw must be 16-byte aligned");
-    return launch_composite_bwd(z, raw, rays, n_rays, k, white_bkgd, d_rgb, d_depth, d_weights, d_raw, d_z,
-                                (hipStream_t)stream);
+    CompositeBwdCall c;
+    c.z = z; c.raw = raw; c.rays = rays; c.n_rays = n_rays; c.K = k; c.white_bkgd = white_bkgd; c.d_rgb = d_rgb;
+    c.d_depth = d_depth; c.d_weights = d_weights; c.d_raw = d_raw; c.d_z = d_z;
+    return launch_composite_bwd(c, (hipStream_t)stream);
 }
 
 int pnr_points_input_backward_masked(const pnr_scene *scene, const pnr_mlp_desc *desc, const void *packed,
@@ -503,6 +505,13 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
         return c;
     };
     auto launch = [&](const PointMlpCall &c) { return launch_point_mlp(*scene, *desc, c, st); };
+    // the standalone composite of a pass: K samples at z with the MLP's raw outputs
+    auto composite = [&](const float *z, const float *raw, int K, float *weights, float *rgb, float *depth) {
+        CompositeCall cc;
+        cc.z = z; cc.raw = raw; cc.rays = rays->rays; cc.n_rays = n; cc.K = K; cc.white_bkgd = cfg->white_bkgd;
+        cc.weights = weights; cc.rgb = rgb; cc.depth = depth;
+        return launch_composite(cc, st);
+    };
 
     if (route.single) {   // events 0 1 [launch] 2 3 4 5 6
         MarchCfg m = march_pass(cfg, 1, out->coarse_weights, out->coarse_rgb, out->coarse_depth);
@@ -539,9 +548,7 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
         c.out = rawc;
         if ((rc = launch_sample_coarse(rays->rays, n, kc, g.u_coarse, cfg->lindisp, zc, st))) return rc;
         if ((rc = mark(1)) || (rc = launch(c)) || (rc = mark(2))) return rc;
-        if ((rc = launch_composite(zc, rawc, rays->rays, n, kc, cfg->white_bkgd, wc, out->coarse_rgb,
-                                   out->coarse_depth, st)))
-            return rc;
+        if ((rc = composite(zc, rawc, kc, wc, out->coarse_rgb, out->coarse_depth))) return rc;
     }
     if ((rc = mark(3)) || kf == 0) return rc;
 
@@ -550,10 +557,13 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
     float *rawf = reinterpret_cast<float *>(ws + w.raw_f);
     int *origin = route.reuse ? reinterpret_cast<int *>(ws + w.origin) : nullptr;
     float *z_new = route.reuse ? reinterpret_cast<float *>(ws + w.z_new) : nullptr;
-    if (!route.fuse_s &&
-        (rc = launch_sample_fine(rays->rays, n, kc, zc, wc, out->coarse_depth, kf, kfd, cfg->depth_std, g.u_fine,
-                                 g.u_jit, g.n_depth, cfg->lindisp, zf, st, origin, z_new)))
-        return rc;
+    if (!route.fuse_s) {
+        FineSampleCall f;
+        f.rays = rays->rays; f.n_rays = n; f.kc = kc; f.z_coarse = zc; f.weights = wc; f.depth = out->coarse_depth;
+        f.kf = kf; f.kfd = kfd; f.depth_std = cfg->depth_std; f.u_fine = g.u_fine; f.u_jit = g.u_jit;
+        f.n_depth = g.n_depth; f.lindisp = cfg->lindisp; f.z_fine = zf; f.origin = origin; f.z_new = z_new;
+        if ((rc = launch_sample_fine(f, st))) return rc;
+    }
     if ((rc = mark(4))) return rc;
     if (route.fuse_f) {
         const MarchCfg m = march_pass(cfg, kall / 64, out->fine_weights, out->fine_rgb, out->fine_depth);
@@ -573,9 +583,7 @@ int pnr_render_forward_proj(const pnr_scene *scene, const pnr_mlp_desc *desc, co
         if ((rc = launch(c))) return rc;
     }
     if ((rc = mark(5))) return rc;
-    if ((rc = launch_composite(zf, rawf, rays->rays, n, kall, cfg->white_bkgd, out->fine_weights, out->fine_rgb,
-                               out->fine_depth, st)))
-        return rc;
+    if ((rc = composite(zf, rawf, kall, out->fine_weights, out->fine_rgb, out->fine_depth))) return rc;
     return mark(6);
 }
 
@@ -603,10 +611,12 @@ int pnr_sample_fine(const float *rays, int64_t n_rays, int32_t n_coarse, const f
     if (!rays || !z_coarse || !coarse_weights || !z_fine) return fail(PNR_ERR_INVALID, "pnr_sample_fine: NULL");
     if (n_fine - n_fine_depth > 0 && (!u_fine || !u_fine_jit)) return fail(PNR_ERR_INVALID, "fine streams NULL");
     if (n_fine_depth > 0 && (!n_depth || !coarse_depth)) return fail(PNR_ERR_INVALID, "depth inputs NULL");
-    return launch_sample_fine(rays, n_rays, n_coarse, z_coarse, coarse_weights, coarse_depth, n_fine,
-                              n_fine_depth, depth_std, RngSrc{u_fine, 0, 0, PNR_RNG_U_FINE},
-                              RngSrc{u_fine_jit, 0, 0, PNR_RNG_U_FINE_JIT}, RngSrc{n_depth, 0, 0, PNR_RNG_N_DEPTH},
-                              lindisp, z_fine, (hipStream_t)stream);
+    FineSampleCall c;
+    c.rays = rays; c.n_rays = n_rays; c.kc = n_coarse; c.z_coarse = z_coarse; c.weights = coarse_weights;
+    c.depth = coarse_depth; c.kf = n_fine; c.kfd = n_fine_depth; c.depth_std = depth_std;
+    c.u_fine = RngSrc{u_fine, 0, 0, PNR_RNG_U_FINE}; c.u_jit = RngSrc{u_fine_jit, 0, 0, PNR_RNG_U_FINE_JIT};
+    c.n_depth = RngSrc{n_depth, 0, 0, PNR_RNG_N_DEPTH}; c.lindisp = lindisp; c.z_fine = z_fine;
+    return launch_sample_fine(c, (hipStream_t)stream);
 }
 
 int pnr_rng_fill(uint64_t seed, uint64_t offset, int32_t stream, int64_t n_rays, int32_t width, float *out,
@@ -624,7 +634,10 @@ int pnr_composite(const float *z, const float *raw, const float *rays, int64_t n
     if (n_rays == 0) return PNR_OK;
     if (!z || !raw || !rays || !rgb || !depth) return fail(PNR_ERR_INVALID, "pnr_composite: NULL");
     if (misaligned(15, raw)) return fail(PNR_ERR_INVALID, "raw must be 16-byte aligned");
-    return launch_composite(z, raw, rays, n_rays, k, white_bkgd, weights, rgb, depth, (hipStream_t)stream);
+    CompositeCall c;
+    c.z = z; c.raw = raw; c.rays = rays; c.n_rays = n_rays; c.K = k; c.white_bkgd = white_bkgd; c.weights = weights;
+    c.rgb = rgb; c.depth = depth;
+    return launch_composite(c, (hipStream_t)stream);
 }
 
 int pnr_latent_channels_last(const float *const *maps, const int32_t *channels, const int32_t *heights,

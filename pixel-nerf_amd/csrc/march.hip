@@ -20,12 +20,13 @@ __global__ void k_sample_coarse(const float *__restrict__ rays, int64_t n_rays, 
     if (idx >= n_rays * kc) return;
     const int64_t b = idx / kc;
     const int k = (int)(idx - b * kc);
-    z[idx] = coarse_z(u, b, kc, k, rays[b * 8 + 6], rays[b * 8 + 7], lindisp != 0);
+    const float *ray = ray_at(rays, b);
+    z[idx] = coarse_z(u, b, kc, k, ray[RAY_NEAR], ray[RAY_FAR], lindisp != 0);
 }
 
 // ---------------------------------------------------------------------------
 // sample_fine + sample_fine_depth + sort — nerf.py:120-161, 284-295 (sample_fine_wave)
-// One 64-lane block per ray.  LDS: cdf[Kc+1] then the sort buffer[N].
+// One 64-lane block per ray.  LDS: fine_lds (march_dev.h).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_sample_fine(
     const float *__restrict__ rays, int kc, const float *__restrict__ z_coarse,
@@ -34,14 +35,13 @@ __global__ __launch_bounds__(64) void k_sample_fine(
     int n_sort, float *__restrict__ z_fine,
     int *__restrict__ origin, float *__restrict__ z_new) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *cdf = smem;            // kc + 1
-    float *s = smem + kc + 1;     // n_sort (power of two >= kc + kf)
-    int *si = reinterpret_cast<int *>(s + n_sort);   // origin of each sorted value (origin != NULL)
+    const FineLds L = fine_lds(kc, n_sort, origin != nullptr);
     const int lane = threadIdx.x;
     const int64_t b = blockIdx.x;
-    sample_fine_wave(lane, b, rays[b * 8 + 6], rays[b * 8 + 7], kc, weights + b * kc, z_coarse + b * kc,
+    const float *ray = ray_at(rays, b);
+    sample_fine_wave(lane, b, ray[RAY_NEAR], ray[RAY_FAR], kc, weights + b * kc, z_coarse + b * kc,
                      kfd > 0 ? depth[b] : 0.f, kf, kfd, depth_std, u_fine, u_jit, n_depth, lindisp != 0, n_sort,
-                     cdf, s, si, z_fine, origin, z_new);
+                     smem + L.cdf, smem + L.sort, reinterpret_cast<int *>(smem + L.origin), z_fine, origin, z_new);
 }
 
 // raw_f[b][k] = raw of sorted fine sample k: the coarse pass's output for a coarse sample
@@ -60,12 +60,7 @@ __global__ __launch_bounds__(256) void k_merge_raw(const int *__restrict__ origi
 }
 
 // ---------------------------------------------------------------------------
-// composite — nerf.py:176-249 (composite_wave, march_dev.h)
-//   delta_i = z_{i+1} - z_i, delta_last = far - z_last
-//   alpha = 1 - exp(-delta * relu(sigma));  T = excl. cumprod(1 - alpha + 1e-10)
-//   w = alpha * T;  rgb = sum w c;  depth = sum w z;  white: rgb += 1 - sum w
-// One wave per ray, 4 rays per 256-thread block; the cumprod accumulates in double
-// (torch's CPU cumprod accumulates in double and rounds each prefix).
+// composite — nerf.py:176-249: the formulas are stated in march_dev.h (composite_wave).
 // ---------------------------------------------------------------------------
 // K <= 256: one wave per two rays, lane l loads samples 64 i + l of both (1 KB of raw per load
 // instruction), all loads issued before the first wait (clamped addresses), then composite_wave
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(256) void k_composite_c(
 #pragma unroll
     for (int j = 0; j < RPW; ++j) {
         const int64_t b = b0 + j < n_rays ? b0 + j : n_rays - 1;
-        far[j] = rays[b * 8 + 7];
+        far[j] = ray_at(rays, b)[RAY_FAR];
         const float *zr = z + b * K;
         const f4 *rr = reinterpret_cast<const f4 *>(raw) + b * K;
 #pragma unroll
@@ -103,7 +98,9 @@ __global__ __launch_bounds__(256) void k_composite_c(
     }
 }
 
-// any K: 64-sample chunks, one wave scan per chunk with a running carry
+// any K: one wave per ray, 64-sample chunks, one wave scan per chunk with a running carry.  Its scan
+// (__shfl_up) and its sums (wave_sum) associate differently from composite_wave's DPP forms, so it
+// keeps them: swapping either would change its results in the last bits.
 __global__ __launch_bounds__(256) void k_composite(
     const float *__restrict__ z, const float *__restrict__ raw, const float *__restrict__ rays,
     int64_t n_rays, int K, int white_bkgd, float *__restrict__ weights,
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(256) void k_composite(
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_rays) return;
-    const float far = rays[b * 8 + 7];
+    const float far = ray_at(rays, b)[RAY_FAR];
     const float *zr = z + b * K;
     const f4 *rr = reinterpret_cast<const f4 *>(raw) + b * K;
     double carry = 1.0;
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(256) void k_gen_rays(const float *__restrict__ pose
         d[r] = add_rn(add_rn(mul_rn(P[4 * r], u0), mul_rn(P[4 * r + 1], u1)), mul_rn(P[4 * r + 2], u2));
     a = f4{P[3], P[7], P[11], d[0]};
     b = f4{d[1], d[2], near, far};
-    f4 *o = reinterpret_cast<f4 *>(out + i * 8);
+    f4 *o = reinterpret_cast<f4 *>(out + i * RAY_STRIDE);
     o[0] = a;
     o[1] = b;
 }
@@ -203,12 +200,7 @@ __global__ __launch_bounds__(256) void k_gen_rays(const float *__restrict__ pose
 // ---------------------------------------------------------------------------
 int launch_sample_coarse(const float *rays, int64_t n_rays, int kc, const RngSrc &u, int lindisp,
                          float *z, hipStream_t st) {
-    const int64_t n = n_rays * kc;
-    if (n == 0) return PNR_OK;
-    const int64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_sample_coarse, dim3((unsigned)blocks), dim3(256), 0, st, rays, n_rays,
-                       kc, u, lindisp, z);
-    return launch_ok("sample_coarse") ? PNR_OK : PNR_ERR_HIP;
+    return launch_flat("sample_coarse", k_sample_coarse, n_rays * kc, 256, 256, 0, st, rays, n_rays, kc, u, lindisp, z);
 }
 
 int sort_width(int n) {
@@ -217,51 +209,35 @@ int sort_width(int n) {
     return p;
 }
 
-int launch_sample_fine(const float *rays, int64_t n_rays, int kc, const float *z_coarse,
-                       const float *weights, const float *depth, int kf, int kfd,
-                       float depth_std, const RngSrc &u_fine, const RngSrc &u_jit,
-                       const RngSrc &n_depth, int lindisp, float *z_fine, hipStream_t st,
-                       int *origin, float *z_new) {
-    if (n_rays == 0) return PNR_OK;
-    const int n_sort = sort_width(kc + kf);
-    const size_t lds = sizeof(float) * (size_t)(kc + 1 + (origin ? 2 : 1) * n_sort);
-    hipLaunchKernelGGL(k_sample_fine, dim3((unsigned)n_rays), dim3(64), lds, st, rays, kc,
-                       z_coarse, weights, depth, kf, kfd, depth_std, u_fine, u_jit, n_depth,
-                       lindisp, n_sort, z_fine, origin, z_new);
-    return launch_ok("sample_fine") ? PNR_OK : PNR_ERR_HIP;
+int launch_sample_fine(const FineSampleCall &c, hipStream_t st) {
+    const int n_sort = sort_width(c.kc + c.kf);
+    return launch_flat("sample_fine", k_sample_fine, c.n_rays, 1, 64, fine_lds(c.kc, n_sort, c.origin != nullptr).bytes,
+                       st, c.rays, c.kc, c.z_coarse, c.weights, c.depth, c.kf, c.kfd, c.depth_std, c.u_fine, c.u_jit,
+                       c.n_depth, c.lindisp, n_sort, c.z_fine, c.origin, c.z_new);
 }
 
 int launch_merge_raw(const int *origin, const float *raw_c, const float *raw_new, int64_t n_rays, int kc, int kf,
                      float *raw_f, hipStream_t st) {
     const int64_t n = n_rays * (kc + kf);
-    if (n == 0) return PNR_OK;
-    hipLaunchKernelGGL(k_merge_raw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, origin,
-                       reinterpret_cast<const f4 *>(raw_c), reinterpret_cast<const f4 *>(raw_new), n, kc, kf,
-                       reinterpret_cast<f4 *>(raw_f));
-    return launch_ok("merge_raw") ? PNR_OK : PNR_ERR_HIP;
+    return launch_flat("merge_raw", k_merge_raw, n, 256, 256, 0, st, origin, reinterpret_cast<const f4 *>(raw_c),
+                       reinterpret_cast<const f4 *>(raw_new), n, kc, kf, reinterpret_cast<f4 *>(raw_f));
 }
 
-int launch_composite(const float *z, const float *raw, const float *rays, int64_t n_rays, int K,
-                     int white_bkgd, float *weights, float *rgb, float *depth, hipStream_t st) {
-    if (n_rays == 0) return PNR_OK;
-    const int nch = (K + 63) / 64;
+int launch_composite(const CompositeCall &c, hipStream_t st) {
+    const int nch = (c.K + 63) / 64;
     // 4 waves per block: k_composite_c marches two rays per wave, the generic k_composite one
-    const int64_t grid = nch <= 4 ? (n_rays + 7) / 8 : (n_rays + 3) / 4;
     auto kern = nch == 1 ? k_composite_c<1> : nch == 2 ? k_composite_c<2> : nch == 3 ? k_composite_c<3>
               : nch == 4 ? k_composite_c<4> : k_composite;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, z, raw, rays,
-                       n_rays, K, white_bkgd, weights, rgb, depth);
-    return launch_ok("composite") ? PNR_OK : PNR_ERR_HIP;
+    return launch_flat("composite", kern, c.n_rays, nch <= 4 ? 8 : 4, 256, 0, st, c.z, c.raw, c.rays, c.n_rays, c.K,
+                       c.white_bkgd, c.weights, c.rgb, c.depth);
 }
 
 int launch_gen_rays(const float *poses, int64_t n_images, int pose_rows, int width, int height,
                     float fx, float fy, float cx, float cy, float near, float far, float *rays,
                     hipStream_t st) {
     const int64_t n = n_images * width * height;
-    if (n == 0) return PNR_OK;
-    hipLaunchKernelGGL(k_gen_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, poses, pose_rows,
-                       n, width, height, fx, fy, cx, cy, near, far, rays);
-    return launch_ok("gen_rays") ? PNR_OK : PNR_ERR_HIP;
+    return launch_flat("gen_rays", k_gen_rays, n, 256, 256, 0, st, poses, pose_rows, n, width, height, fx, fy, cx, cy,
+                       near, far, rays);
 }
 
 // ---------------------------------------------------------------------------
@@ -277,10 +253,7 @@ __global__ __launch_bounds__(256) void k_rng_fill(const RngSrc r, int64_t n_rays
 }
 
 int launch_rng_fill(const RngSrc &r, int64_t n_rays, int width, float *out, hipStream_t st) {
-    const int64_t n = n_rays * width;
-    if (n == 0) return PNR_OK;
-    hipLaunchKernelGGL(k_rng_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r, n_rays, width, out);
-    return launch_ok("rng_fill") ? PNR_OK : PNR_ERR_HIP;
+    return launch_flat("rng_fill", k_rng_fill, n_rays * width, 256, 256, 0, st, r, n_rays, width, out);
 }
 
 }  // namespace pnr

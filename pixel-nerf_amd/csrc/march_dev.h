@@ -52,6 +52,11 @@ __device__ __forceinline__ float coarse_z(const RngSrc &u, int64_t b, int kc, in
 //   delta_i = z_{i+1} - z_i, delta_last = far - z_last
 //   alpha = 1 - exp(-delta * relu(sigma));  T = excl. cumprod(1 - alpha + 1e-10)
 //   w = alpha * T;  rgb = sum w c;  depth = sum w z;  white: rgb += 1 - sum w
+// (the one statement of these formulas: the generic k_composite of march.hip and k_composite_bwd of
+// train.hip refer here.  Each of the three keeps its own per-sample lines: a shared helper, even one
+// holding the same expressions, moved the register allocation of every marching k_point_mlp and the
+// FMA contraction of k_composite_bwd, profiles/march_refactor)
+//
 // K <= 64 S (S = ceil(K / 64) chunks): lane l holds samples 64 i + l of chunk i (zk, v; lanes past
 // K hold clamped copies), so a ray's loads are lane-contiguous (1 KB of raw per instruction from
 // HBM, conflict-free from LDS).  One exclusive double product scan per chunk (torch's CPU cumprod
@@ -113,43 +118,28 @@ __device__ __forceinline__ float composite_wave(int lane, int64_t b, int K, floa
     return sd;
 }
 
-// ---- cross-lane helpers of the sort / scans (VALU only: DPP and gfx950 permlane swaps) -------
-__device__ __forceinline__ double wave_scan_add(double x) {   // inclusive sum scan over 64 lanes
-    x += dpp_d<0x111>(0.0, x);          // row_shr:1
-    x += dpp_d<0x112>(0.0, x);          // row_shr:2
-    x += dpp_d<0x114>(0.0, x);          // row_shr:4
-    x += dpp_d<0x118>(0.0, x);          // row_shr:8
-    x += dpp_d<0x142, 0xa>(0.0, x);     // row_bcast:15 -> rows 1, 3
-    x += dpp_d<0x143, 0xc>(0.0, x);     // row_bcast:31 -> rows 2, 3
-    return x;
-}
-__device__ __forceinline__ double readlane_d(double x, int l) {
-    const long long v = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)v, l), hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
+// ---- cross-lane helpers of the sort (the scans: wave_scan_add, readlane_d, pnr_common.h) -------
 // value of lane ^ J.  ds_bpermute (__shfl_xor): a DPP / v_permlane{16,32}_swap version of this
 // exchange measured wrong results once the epilogue was inlined inside k_point_mlp's GEMM
 // region (deterministically; bit-exact elsewhere), so the sort keeps the LDS-crossbar permute.
 template <int J>
-__device__ __forceinline__ float lane_xor(float v, int lane) {
-    (void)lane;
+__device__ __forceinline__ float lane_xor(float v) {
     return __shfl_xor(v, J, 64);
 }
 // one compare-exchange stage of a bitonic sort (element e of the sequence, merge size k)
 template <int J>
-__device__ __forceinline__ float bitonic_step(float v, int e, int k, int lane) {
-    const float p = lane_xor<J>(v, lane);
+__device__ __forceinline__ float bitonic_step(float v, int e, int k) {
+    const float p = lane_xor<J>(v);
     return ((e & J) == 0) == ((e & k) == 0) ? fminf(v, p) : fmaxf(v, p);
 }
-__device__ __forceinline__ float bitonic_step_j(float v, int e, int k, int j, int lane) {
+__device__ __forceinline__ float bitonic_step_j(float v, int e, int k, int j) {
     switch (j) {
-    case 1: return bitonic_step<1>(v, e, k, lane);
-    case 2: return bitonic_step<2>(v, e, k, lane);
-    case 4: return bitonic_step<4>(v, e, k, lane);
-    case 8: return bitonic_step<8>(v, e, k, lane);
-    case 16: return bitonic_step<16>(v, e, k, lane);
-    default: return bitonic_step<32>(v, e, k, lane);
+    case 1: return bitonic_step<1>(v, e, k);
+    case 2: return bitonic_step<2>(v, e, k);
+    case 4: return bitonic_step<4>(v, e, k);
+    case 8: return bitonic_step<8>(v, e, k);
+    case 16: return bitonic_step<16>(v, e, k);
+    default: return bitonic_step<32>(v, e, k);
     }
 }
 // ascending bitonic sort of the 64 N values held as v[h] = element 64 h + lane, in registers
@@ -165,7 +155,7 @@ __device__ __forceinline__ void sort_lanes(float (&v)[N], int lane) {
                 v[N - 1] = hi;
             } else {
 #pragma unroll
-                for (int h = 0; h < N; ++h) v[h] = bitonic_step_j(v[h], 64 * h + lane, k, j, lane);
+                for (int h = 0; h < N; ++h) v[h] = bitonic_step_j(v[h], 64 * h + lane, k, j);
             }
         }
     }
@@ -181,6 +171,21 @@ __device__ __forceinline__ void sort_lanes(float (&v)[N], int lane) {
 struct FineDraws {
     float u, uj, nd;
 };
+// k_sample_fine's dynamic LDS, as float offsets from its base: cdf | s | si (si only with origin).
+// The kernel and its launcher both take it from here.  (k_point_mlp's epilogue keeps fixed offsets
+// into its own scratch, kc <= 64 and n_sort <= 128: march_ray in mlp.hip.)
+struct FineLds {
+    ptrdiff_t cdf, sort, origin;
+    size_t bytes;
+};
+__host__ __device__ inline FineLds fine_lds(int kc, int n_sort, bool with_origin) {
+    FineLds l;
+    l.cdf = 0;
+    l.sort = (ptrdiff_t)kc + 1;
+    l.origin = l.sort + n_sort;
+    l.bytes = sizeof(float) * (size_t)(l.origin + (with_origin ? n_sort : 0));
+    return l;
+}
 __device__ __forceinline__ FineDraws fine_draws(int lane, int64_t b, int kf, int kfd, const RngSrc &u_fine,
                                                 const RngSrc &u_jit, const RngSrc &n_depth) {
     const int nf = kf - kfd;

@@ -9,9 +9,6 @@ namespace pnr {
 
 constexpr int64_t kMaxCount = 0x7fffffff;   // int32 indices
 
-// workgroups of `threads` that cover n elements
-inline unsigned blocks(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
-
 // x - x is 0 for a finite x and NaN for +-inf or NaN
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
     const float s = (x - x) + (y - y) + (z - z);

@@ -139,7 +139,9 @@ __device__ __forceinline__ void march_ray(const Args &a, int64_t b, const float 
         for (int i = 0; i < S; ++i) w[64 * i + lane] = wk[i];
         wave_lds_sync();
         // single launch: the sorted fine depths also go to buf's z region (whose coarse depths
-        // composite_wave and the sort's inputs have consumed) for the ray's fine tiles
+        // composite_wave and the sort's inputs have consumed) for the ray's fine tiles.
+        // scr + 128 / scr + 256: this epilogue's fixed form of FineLds (march_dev.h) behind the ray's 128
+        // weights, cdf (kc + 1 <= 65 floats) then the sort buffer (n_sort <= 128); no origin here
         sample_fine_wave(lane, b, near, far, COLS * S, w, buf, depth, kf, c->kfd, c->depth_std, RngSrc{}, RngSrc{},
                          RngSrc{}, c->lindisp != 0, c->n_sort, scr + 128, scr + 256, nullptr, c->z_fine, nullptr,
                          nullptr, true, d, c->single ? const_cast<float *>(buf) : nullptr);
@@ -313,18 +315,8 @@ __global__ __launch_bounds__(NTHR) void k_point_mlp(Args a) {
     // of two MLPs may carry different tables); visible after the first barrier
     float *petab_f = inbuf + M.petab_f;
     if (single && wave == 1) petab_f[lane & 31] = march_cfg(a)->packed_f[lane & 31];
-    // the projection's launch constants (models.py:206-212 -> encoder.py:95-108): the latent size as
-    // floats, the pixel -> grid scales and the half extents
-    struct ProjK {
-        float wlf, hlf, kx, ky, hx, hy;
-    };
-    auto proj_consts = [&]() -> ProjK {
-        const float wlf = (float)a.wl, hlf = (float)a.hl;
-        const float lsx = mul_rn(__fdiv_rn(wlf, sub_rn(wlf, 1.f)), 2.f);
-        const float lsy = mul_rn(__fdiv_rn(hlf, sub_rn(hlf, 1.f)), 2.f);
-        return ProjK{wlf, hlf, __fdiv_rn(lsx, a.img_w), __fdiv_rn(lsy, a.img_h), mul_rn(sub_rn(wlf, 1.f), 0.5f),
-                     mul_rn(sub_rn(hlf, 1.f), 0.5f)};
-    };
+    // the projection's launch constants (proj_consts, pnr_common.h)
+    auto proj_consts = [&]() -> ProjK { return pnr::proj_consts(a.wl, a.hl, a.img_w, a.img_h); };
     // LEAN: ltab, the launch constants that a tile's features need, computed once (every lane
     // computes the same values; wave 0 stores them, visible after the first barrier).  Computed in
     // the loop they are hoisted out of it as uniform floats in VGPRs that live across every tile,

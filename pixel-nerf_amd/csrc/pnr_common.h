@@ -53,6 +53,25 @@ __device__ __forceinline__ float t_to_z(float t, float near, float far, bool lin
     return __fdiv_rn(1.0f, inv);
 }
 
+// ---- a ray: 8 floats [origin 0..2, direction 3..5, near, far] (pnr_abi.h) ----------------------
+constexpr int RAY_STRIDE = 8, RAY_DIR = 3, RAY_NEAR = 6, RAY_FAR = 7;
+__host__ __device__ __forceinline__ const float *ray_at(const float *rays, int64_t b) { return rays + b * RAY_STRIDE; }
+
+// ---- the projection's launch constants (models.py:206-212 -> encoder.py:95-108) -------------------
+// The latent size as floats, the pixel -> grid scales (k = 2 l / (l - 1) / image size, so that
+// grid = pixel k - 1) and the half extents (index = (grid + 1) h).  k_point_mlp's feature phase and
+// the training backward (point_geo and the dz chain of k_points_in_bwd) take them from here.
+struct ProjK {
+    float wlf, hlf, kx, ky, hx, hy;
+};
+__device__ __forceinline__ ProjK proj_consts(int wl, int hl, float img_w, float img_h) {
+    const float wlf = (float)wl, hlf = (float)hl;
+    const float lsx = mul_rn(__fdiv_rn(wlf, sub_rn(wlf, 1.f)), 2.f);
+    const float lsy = mul_rn(__fdiv_rn(hlf, sub_rn(hlf, 1.f)), 2.f);
+    return ProjK{wlf, hlf, __fdiv_rn(lsx, img_w), __fdiv_rn(lsy, img_h), mul_rn(sub_rn(wlf, 1.f), 0.5f),
+                 mul_rn(sub_rn(hlf, 1.f), 0.5f)};
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
@@ -85,15 +104,30 @@ __device__ __forceinline__ double wave_scan_mul(double x) {
 }
 // value of lane - 1 (lane 0: `first`)
 __device__ __forceinline__ double wave_shr1(double x, double first) { return dpp_d<0x138>(first, x); }
+// inclusive sum scan over the 64 lanes, float or double
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ float dpp(float old, float src) { return dpp_f<CTRL, ROW_MASK>(old, src); }
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ double dpp(double old, double src) { return dpp_d<CTRL, ROW_MASK>(old, src); }
+template <typename T>
+__device__ __forceinline__ T wave_scan_add(T x) {
+    x += dpp<0x111>(T(0), x);           // row_shr:1
+    x += dpp<0x112>(T(0), x);           // row_shr:2
+    x += dpp<0x114>(T(0), x);           // row_shr:4
+    x += dpp<0x118>(T(0), x);           // row_shr:8
+    x += dpp<0x142, 0xa>(T(0), x);      // row_bcast:15 -> rows 1, 3
+    x += dpp<0x143, 0xc>(T(0), x);      // row_bcast:31 -> rows 2, 3
+    return x;
+}
+// lane l's value of a double, wave-uniform (low word read first)
+__device__ __forceinline__ double readlane_d(double x, int l) {
+    const long long v = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_readlane((int)v, l), hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
 // sum over the 64 lanes, returned wave-uniform
 __device__ __forceinline__ float wave_sum_dpp(float x) {
-    x += dpp_f<0x111>(0.f, x);
-    x += dpp_f<0x112>(0.f, x);
-    x += dpp_f<0x114>(0.f, x);
-    x += dpp_f<0x118>(0.f, x);
-    x += dpp_f<0x142, 0xa>(0.f, x);
-    x += dpp_f<0x143, 0xc>(0.f, x);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_scan_add(x)), 63));
 }
 
 __device__ __forceinline__ float wave_max(float v) {

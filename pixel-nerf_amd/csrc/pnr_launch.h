@@ -1,8 +1,9 @@
-// Host launchers and size helpers behind the C ABI (abi.cpp), each declared once with its default
-// arguments and with the parameter names of its definition.  Every .hip file that defines one
-// includes this header, so a definition whose types drift from its declaration fails to compile.
-// The fused MLP's launchers take their buffers as a struct of named fields (PointMlpCall for the
-// forward, MlpBwdCall for the training backward), then the stream.
+// Host launchers and size helpers behind the C ABI (abi.cpp), each declared once with the parameter
+// names of its definition.  Every .hip file that defines one includes this header, so a definition
+// whose types drift from its declaration fails to compile.  A launcher with many buffers takes them
+// as a struct of named fields (FineSampleCall, CompositeCall and CompositeBwdCall for the ray march,
+// PointMlpCall for the fused MLP's forward, MlpBwdCall for its training backward); the stream is
+// every launcher's last parameter.  launch_flat is the one spelling of a flat launch.
 #pragma once
 #include "pnr_common.h"
 
@@ -10,20 +11,57 @@ namespace pnr {
 
 struct MarchCfg;   // march_dev.h
 
+// workgroups of `threads` that cover n elements
+inline unsigned blocks(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+// A flat launch: nothing when n == 0, else the workgroups of `threads` that cover n items at `per_block`
+// items each, `lds` bytes of dynamic LDS, and the launch status as a PNR_* code.
+template <typename Kernel, typename... Args>
+inline int launch_flat(const char *what, Kernel kern, int64_t n, int per_block, int threads, size_t lds,
+                       hipStream_t st, Args... args) {
+    if (n == 0) return PNR_OK;
+    hipLaunchKernelGGL(kern, dim3(blocks((size_t)n, per_block)), dim3(threads), lds, st, args...);
+    return launch_ok(what) ? PNR_OK : PNR_ERR_HIP;
+}
+
 // march.hip
 int launch_sample_coarse(const float *rays, int64_t n_rays, int kc, const RngSrc &u, int lindisp, float *z,
                          hipStream_t st);
-int launch_sample_fine(const float *rays, int64_t n_rays, int kc, const float *z_coarse, const float *weights,
-                       const float *depth, int kf, int kfd, float depth_std, const RngSrc &u_fine,
-                       const RngSrc &u_jit, const RngSrc &n_depth, int lindisp, float *z_fine, hipStream_t st,
-                       int *origin = nullptr, float *z_new = nullptr);
+// sample_fine + sample_fine_depth + sort of n_rays rays: kc coarse samples in, kc + kf sorted depths out
+struct FineSampleCall {
+    const float *rays = nullptr;       // (n_rays, 8)
+    int64_t n_rays = 0;
+    int kc = 0;
+    const float *z_coarse = nullptr;   // (n_rays, kc)
+    const float *weights = nullptr;    // (n_rays, kc) coarse weights
+    const float *depth = nullptr;      // (n_rays) coarse depth (read when kfd > 0)
+    int kf = 0, kfd = 0;               // new samples, and how many of them are depth samples
+    float depth_std = 0.f;
+    RngSrc u_fine{}, u_jit{}, n_depth{};
+    int lindisp = 0;
+    float *z_fine = nullptr;           // (n_rays, kc + kf), sorted
+    int *origin = nullptr;             // NULL, or (n_rays, kc + kf): each value's index in cat(coarse, new)
+    float *z_new = nullptr;            // with origin: (n_rays, kf), the new samples in draw order
+};
+int launch_sample_fine(const FineSampleCall &c, hipStream_t st);
+// the alpha composite of n_rays rays x K samples
+struct CompositeCall {
+    const float *z = nullptr;          // (n_rays, K)
+    const float *raw = nullptr;        // (n_rays, K, 4) rgb, sigma
+    const float *rays = nullptr;       // (n_rays, 8)
+    int64_t n_rays = 0;
+    int K = 0;
+    int white_bkgd = 0;
+    float *weights = nullptr;          // (n_rays, K), or NULL
+    float *rgb = nullptr;              // (n_rays, 3)
+    float *depth = nullptr;            // (n_rays)
+};
+int launch_composite(const CompositeCall &c, hipStream_t st);
 int launch_rng_fill(const RngSrc &r, int64_t n_rays, int width, float *out, hipStream_t st);
 int launch_merge_raw(const int *origin, const float *raw_c, const float *raw_new, int64_t n_rays, int kc, int kf,
                      float *raw_f, hipStream_t st);
 int launch_gen_rays(const float *poses, int64_t n_images, int pose_rows, int width, int height, float fx, float fy,
                     float cx, float cy, float near, float far, float *rays, hipStream_t st);
-int launch_composite(const float *z, const float *raw, const float *rays, int64_t n_rays, int K, int white_bkgd,
-                     float *weights, float *rgb, float *depth, hipStream_t st);
 int sort_width(int n);
 // mlp_pack.hip
 size_t mlp_packed_bytes(const pnr_mlp_desc &d);
@@ -87,9 +125,19 @@ int launch_latent_cl(const float *const *maps, const int32_t *channels, const in
                      const int32_t *widths, int n_maps, int n_images, float *latent_cl, int out_h, int out_w,
                      bool nhwc, hipStream_t st);
 // train.hip
-int launch_composite_bwd(const float *z, const float *raw, const float *rays, int64_t n_rays, int K,
-                         int white_bkgd, const float *d_rgb, const float *d_depth, const float *d_weights,
-                         float *d_raw, float *d_z, hipStream_t st);
+// the composite's backward (K <= 256): the forward's inputs, the output gradients, the input gradients
+struct CompositeBwdCall {
+    const float *z = nullptr, *raw = nullptr, *rays = nullptr;   // as CompositeCall
+    int64_t n_rays = 0;
+    int K = 0;
+    int white_bkgd = 0;
+    const float *d_rgb = nullptr;      // (n_rays, 3)
+    const float *d_depth = nullptr;    // (n_rays), or NULL
+    const float *d_weights = nullptr;  // (n_rays, K), or NULL
+    float *d_raw = nullptr;            // (n_rays, K, 4)
+    float *d_z = nullptr;              // (n_rays, K), or NULL
+};
+int launch_composite_bwd(const CompositeBwdCall &c, hipStream_t st);
 int launch_points_in_bwd(const pnr_scene &sc, const pnr_rays &rays, const float *zs, int K, const float *pe,
                          int pe_n, const float *d_feat, const float *d_zlat, float *d_latent, float *d_z,
                          const uint8_t *z_mask, hipStream_t st);

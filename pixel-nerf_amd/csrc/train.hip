@@ -10,7 +10,7 @@
 //                     code.py:38, and the projection, models.py:206-212)
 // The ResnetFC backward is mlp_bwd.hip (the fused f16x3 chain) and wgrad.hip (weight gradients);
 // the fp32 / bf16 models run it as per-layer torch GEMMs on the saved activations (pnr/train.py).
-#include "pnr_common.h"
+#include "march_dev.h"
 #include "pnr_launch.h"
 
 namespace pnr {
@@ -19,6 +19,7 @@ namespace pnr {
 // composite backward (K <= 64 S; lane l owns the S consecutive samples S l .. S l + S - 1, so the
 // suffix sum runs inside the lane and then over lanes; the forward's k_composite_c instead uses
 // lane-strided chunks, lane l holding samples 64 i + l)
+// The forward's formulas: march_dev.h (composite).
 //   w_i = a_i T_i,  T_i = prod_{j<i} s_j,  s_j = 1 - a_j + 1e-10,  a = 1 - exp(-delta relu(sigma))
 //   g_i = dL/dw_i = d_rgb . c_i + d_depth z_i (- sum d_rgb if white_bkgd) + d_weights_i
 //   da_i = g_i T_i - (sum_{k>i} g_k w_k) / s_i
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_rays) return;
-    const float far = rays[b * 8 + 7];
+    const float far = ray_at(rays, b)[RAY_FAR];
     const float *zr = z + b * K;
     const f4 *rr = reinterpret_cast<const f4 *>(raw) + b * K;
     const int k0 = S * lane;
@@ -82,13 +83,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(
     // inclusive scan over the lanes in reverse order.  The terms decay with the transmittance, and
     // the sum is divided by s_i below, which is as small as 1e-10 behind an opaque sample: taken as
     // total - prefix its rounding error (2^-24 of the ray's total) came out 1 / s_i times larger.
-    float incl = __shfl(gw_local, 63 - lane, 64);   // reversed lane r holds lane 63 - r
-    incl += dpp_f<0x111>(0.f, incl);
-    incl += dpp_f<0x112>(0.f, incl);
-    incl += dpp_f<0x114>(0.f, incl);
-    incl += dpp_f<0x118>(0.f, incl);
-    incl += dpp_f<0x142, 0xa>(0.f, incl);
-    incl += dpp_f<0x143, 0xc>(0.f, incl);
+    const float incl = wave_scan_add(__shfl(gw_local, 63 - lane, 64));   // reversed lane r holds lane 63 - r
     // sum over the lanes after this one: lanes l + 1 .. 63 are reversed lanes 0 .. 62 - l
     float after = __shfl(incl, (62 - lane) & 63, 64);
     if (lane == 63) after = 0.f;
@@ -150,11 +145,11 @@ __device__ __forceinline__ PointGeo point_geo(const float *__restrict__ rays, co
                                               float img_w, float img_h, int64_t p, int ns, int v) {
     PointGeo G;
     const int64_t b = p / K;
-    const float *ray = rays + b * 8;
+    const float *ray = ray_at(rays, b);
     const float zz = zs[p];
-    const float px = add_rn(ray[0], mul_rn(zz, ray[3]));
-    const float py = add_rn(ray[1], mul_rn(zz, ray[4]));
-    const float pz = add_rn(ray[2], mul_rn(zz, ray[5]));
+    const float px = add_rn(ray[0], mul_rn(zz, ray[RAY_DIR]));
+    const float py = add_rn(ray[1], mul_rn(zz, ray[RAY_DIR + 1]));
+    const float pz = add_rn(ray[2], mul_rn(zz, ray[RAY_DIR + 2]));
     const int64_t cv = (b / rays_per_obj) * ns + v;   // camera / latent of (object, view v)
     const float *cam = cams + cv * 16;
 #pragma unroll
@@ -163,18 +158,16 @@ __device__ __forceinline__ PointGeo point_geo(const float *__restrict__ rays, co
         G.xc[i] = add_rn(G.xr[i], cam[9 + i]);
     }
     const float fx = cam[12], fy = cam[13], cx = cam[14], cy = cam[15];
-    // forward projection, as k_point_mlp
+    // forward projection, as k_point_mlp's feature phase: both take the constants from proj_consts
     const float u0 = __fdiv_rn(-G.xc[0], G.xc[2]), v0 = __fdiv_rn(-G.xc[1], G.xc[2]);
     const float u = add_rn(mul_rn(u0, fx), cx), w = add_rn(mul_rn(v0, fy), cy);
-    const float wlf = (float)wl, hlf = (float)hl;
-    const float lsx = mul_rn(__fdiv_rn(wlf, sub_rn(wlf, 1.f)), 2.f);
-    const float lsy = mul_rn(__fdiv_rn(hlf, sub_rn(hlf, 1.f)), 2.f);
-    const float gx = sub_rn(mul_rn(u, __fdiv_rn(lsx, img_w)), 1.f);
-    const float gy = sub_rn(mul_rn(w, __fdiv_rn(lsy, img_h)), 1.f);
-    G.ixu = mul_rn(add_rn(gx, 1.f), mul_rn(sub_rn(wlf, 1.f), 0.5f));
-    G.iyu = mul_rn(add_rn(gy, 1.f), mul_rn(sub_rn(hlf, 1.f), 0.5f));
-    G.ix = fminf(fmaxf(G.ixu, 0.f), wlf - 1.f);
-    G.iy = fminf(fmaxf(G.iyu, 0.f), hlf - 1.f);
+    const ProjK pk = proj_consts(wl, hl, img_w, img_h);
+    const float gx = sub_rn(mul_rn(u, pk.kx), 1.f);
+    const float gy = sub_rn(mul_rn(w, pk.ky), 1.f);
+    G.ixu = mul_rn(add_rn(gx, 1.f), pk.hx);
+    G.iyu = mul_rn(add_rn(gy, 1.f), pk.hy);
+    G.ix = fminf(fmaxf(G.ixu, 0.f), pk.wlf - 1.f);
+    G.iy = fminf(fmaxf(G.iyu, 0.f), pk.hlf - 1.f);
     const int x0 = (int)floorf(G.ix), y0 = (int)floorf(G.iy);
     G.inx1 = x0 + 1 < wl;
     G.iny1 = y0 + 1 < hl;
@@ -281,18 +274,15 @@ __global__ __launch_bounds__(256) void k_points_in_bwd(
         const int64_t p = p0 + lane;
         if (z_mask && !z_mask[p]) continue;   // d_z written 0 below
         const PointGeo G = point_geo(rays, zs, K, rays_per_obj, cams, hl, wl, img_w, img_h, p, ns, v);
-        const float *ray = rays + (p / K) * 8;
+        const float *ray = ray_at(rays, p / K);
         const float *cam = cams + (((p / K) / rays_per_obj) * ns + v) * 16;
         const float fx = cam[12], fy = cam[13];
-        const float wlf = (float)wl, hlf = (float)hl;
-        const float sx = __fdiv_rn(mul_rn(__fdiv_rn(wlf, sub_rn(wlf, 1.f)), 2.f), img_w);
-        const float sy = __fdiv_rn(mul_rn(__fdiv_rn(hlf, sub_rn(hlf, 1.f)), 2.f), img_h);
-        const float hx = mul_rn(sub_rn(wlf, 1.f), 0.5f), hy = mul_rn(sub_rn(hlf, 1.f), 0.5f);
+        const ProjK pk = proj_consts(wl, hl, img_w, img_h);
         // torch clip_coordinates_set_grad: borders count as out of bounds (NaN -> 0)
-        const float gclip_x = (G.ixu > 0.f && G.ixu < wlf - 1.f) ? 1.f : 0.f;
-        const float gclip_y = (G.iyu > 0.f && G.iyu < hlf - 1.f) ? 1.f : 0.f;
-        // projection chain: ix = (gx + 1) hx, gx = u sx - 1, u = -(xc0 / xc2) fx + cx
-        const float du = dix_run * gclip_x * hx * sx, dv = diy_run * gclip_y * hy * sy;
+        const float gclip_x = (G.ixu > 0.f && G.ixu < pk.wlf - 1.f) ? 1.f : 0.f;
+        const float gclip_y = (G.iyu > 0.f && G.iyu < pk.hlf - 1.f) ? 1.f : 0.f;
+        // projection chain: ix = (gx + 1) hx, gx = u kx - 1, u = -(xc0 / xc2) fx + cx
+        const float du = dix_run * gclip_x * pk.hx * pk.kx, dv = diy_run * gclip_y * pk.hy * pk.ky;
         const float inv = 1.f / G.xc[2];
         float dxc[3];
         dxc[0] = -du * fx * inv;
@@ -312,7 +302,7 @@ __global__ __launch_bounds__(256) void k_points_in_bwd(
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const float dxw = cam[i] * dxr[0] + cam[3 + i] * dxr[1] + cam[6 + i] * dxr[2];
-            dzs += dxw * ray[3 + i];
+            dzs += dxw * ray[RAY_DIR + i];
         }
         dz_sum = v == 0 ? dzs : dz_sum + dzs;
     }
@@ -320,29 +310,23 @@ __global__ __launch_bounds__(256) void k_points_in_bwd(
 }
 
 // ---------------------------------------------------------------------------
-int launch_composite_bwd(const float *z, const float *raw, const float *rays, int64_t n_rays, int K,
-                         int white_bkgd, const float *d_rgb, const float *d_depth, const float *d_weights,
-                         float *d_raw, float *d_z, hipStream_t st) {
-    if (n_rays == 0) return PNR_OK;
-    const int nch = (K + 63) / 64;
+int launch_composite_bwd(const CompositeBwdCall &c, hipStream_t st) {
+    const int nch = (c.K + 63) / 64;
     if (nch > 4) return fail(PNR_ERR_UNSUPPORTED, "composite backward: K <= 256");
     auto kern = nch == 1 ? k_composite_bwd<1> : nch == 2 ? k_composite_bwd<2>
               : nch == 3 ? k_composite_bwd<3> : k_composite_bwd<4>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, st, z, raw, rays, n_rays, K,
-                       white_bkgd, d_rgb, d_depth, d_weights, d_raw, d_z);
-    return launch_ok("composite_bwd") ? PNR_OK : PNR_ERR_HIP;
+    return launch_flat("composite_bwd", kern, c.n_rays, 4, 256, 0, st, c.z, c.raw, c.rays, c.n_rays, c.K, c.white_bkgd,
+                       c.d_rgb, c.d_depth, c.d_weights, c.d_raw, c.d_z);
 }
 
 int launch_points_in_bwd(const pnr_scene &sc, const pnr_rays &rays, const float *zs, int K, const float *pe,
                          int pe_n, const float *d_feat, const float *d_zlat, float *d_latent, float *d_z,
                          const uint8_t *z_mask, hipStream_t st) {
     const int64_t n_points = rays.n_rays * K;
-    if (n_points == 0) return PNR_OK;
-    const int64_t waves = (n_points + RUN - 1) / RUN;
-    hipLaunchKernelGGL(k_points_in_bwd, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rays.rays, zs, K,
+    // one wave per run of RUN points, 4 waves per block
+    return launch_flat("points_in_bwd", k_points_in_bwd, n_points, 4 * RUN, 256, 0, st, rays.rays, zs, K,
                        rays.rays_per_obj, n_points, sc.n_views, sc.cams, sc.latent, sc.latent_h, sc.latent_w,
                        sc.image_w, sc.image_h, pe, pe_n, d_feat, d_zlat, d_latent, d_z, z_mask);
-    return launch_ok("points_in_bwd") ? PNR_OK : PNR_ERR_HIP;
 }
 
 }  // namespace pnr

@@ -12,10 +12,17 @@ in another process, which changes the latent in its last bits.
   python tools/bitwise_ab.py save-train OUT.pt  the training backward through the ABI, into buffers pre-filled with a
                                                 fixed pattern (train_cases below): the fused chain's dy / d_zlat /
                                                 d_bias, the weight gradients in both arithmetics, one training step
+  python tools/bitwise_ab.py save-march OUT.pt  the along-ray kernels through the ABI, outputs pre-filled likewise
+                                                (march_cases below): composite, the samplers, the draws, the ray
+                                                generator, the composite and point-input backward, and two renders
+                                                whose fine pass reuses the coarse MLP
   python tools/bitwise_ab.py cmp A.pt B.pt      bitwise equal? (torch.equal per tensor, no tolerance)
   python tools/bitwise_ab.py time OUT.json      HIP-event times of one render of 8,192 rays x (64 + 64)
                                                 per instantiation no bench leg reaches: one warm-up,
-                                                five repeats each (alternate the libraries by process)"""
+                                                five repeats each (alternate the libraries by process)
+  python tools/bitwise_ab.py time-march OUT.json  HIP-event times of the two along-ray kernels no bench leg isolates:
+                                                the generic k_composite (65,536 rays x 320) and k_composite_bwd
+                                                (65,536 x 96 and x 256), three warm-ups and 20 launches each"""
 import json
 import os
 import sys
@@ -333,6 +340,189 @@ def save_train(out):
     print("saved", out, len(blob), "values", os.environ.get("PNR_LIB_PATH", "default"))
 
 
+# ---- the fourth case set: the along-ray kernels --------------------------------------------------
+def march_cases():
+    """Yields (name, tensor), every tensor on the CPU."""
+    import torch
+
+    import march_surface as ms
+    import test_gpu_march_backward as tb
+    import test_gpu_march_range as tr
+    import test_gpu_mlp_lean as tl
+    import test_gpu_parity as tgp
+    from oracle import ref_cpu
+    from pnr import _lib, synth, torchops
+    from pnr.models import PixelNeRFNet
+    from pnr.renderer import NeRFRenderer
+
+    lib = _lib.load()
+    dev = tr.DEV
+    st = lambda: _lib.stream_of(torch.device(dev))   # noqa: E731
+    up = lambda t: None if t is None else t.to(dev).contiguous()   # noqa: E731
+
+    def filled(*shape):
+        return torch.full(shape, FILL, dtype=torch.float32, device=dev)
+
+    # pnr_composite
+    def composite(rays, z, raw, white, want_w=True):
+        B, K = z.shape
+        rays, z, raw = up(rays), up(z), up(raw)
+        w, rgb, d = (filled(B, K) if want_w else None), filled(B, 3), filled(B)
+        _lib.check(lib.pnr_composite(_lib.ptr(z), _lib.ptr(raw), _lib.ptr(rays), B, K, int(white), _lib.ptr(w),
+                                     _lib.ptr(rgb), _lib.ptr(d), st()), "pnr_composite")
+        torch.cuda.synchronize()
+        return {"w": w, "rgb": rgb, "depth": d}
+
+    def each(name, d):
+        for k, v in d.items():
+            if v is not None:
+                yield "%s | %s" % (name, k), v.cpu()
+
+    for B, K in tr.COMPOSITE_CASES:
+        for white in (True, False):
+            yield from each("composite B=%d K=%d white=%d" % (B, K, white), composite(*tr.composite_inputs(B, K), white))
+    for B, K in tr.NULL_WEIGHT_CASES:
+        yield from each("composite no weights B=%d K=%d" % (B, K), composite(*tr.composite_inputs(B, K), True, False))
+    for K in ms.COMPOSITE_KS:
+        yield from each("composite opaque rows K=%d" % K, composite(*ms.composite_rows(K, 100 + K), True))
+
+    # pnr_sample_coarse, pnr_rng_fill, pnr_gen_rays
+    for B, K in ((3, 257), (2, 1024)):
+        for lindisp in (False, True):
+            g = torch.Generator().manual_seed(K)
+            rays = torch.cat([torch.randn(B, 6, generator=g), torch.full((B, 1), 0.8), torch.full((B, 1), 1.8)], 1)
+            u, z = up(torch.rand(B, K, generator=g)), filled(B, K)
+            rays = up(rays)
+            _lib.check(lib.pnr_sample_coarse(_lib.ptr(rays), B, K, _lib.ptr(u), int(lindisp), _lib.ptr(z), st()),
+                       "pnr_sample_coarse")
+            torch.cuda.synchronize()
+            yield "sample_coarse B=%d K=%d lindisp=%d" % (B, K, lindisp), z.cpu()
+    for stream in (_lib.RNG_U_COARSE, _lib.RNG_U_FINE, _lib.RNG_U_FINE_JIT, _lib.RNG_N_DEPTH):
+        out = filled(5, 37)
+        _lib.check(lib.pnr_rng_fill(1234, 3, int(stream), 5, 37, _lib.ptr(out), st()), "pnr_rng_fill")
+        torch.cuda.synchronize()
+        yield "rng_fill stream %d" % stream, out.cpu()
+    poses = synth.srn_poses([10.0, 130.0], phi=-20.0, radius=2.7)
+    for rows in (3, 4):
+        p, out = up(poses[:, :rows]), filled(2 * 5 * 7, 8)
+        _lib.check(lib.pnr_gen_rays(_lib.ptr(p), 2, rows, 7, 5, 9.5, 9.25, 3.4, 2.6, 0.8, 1.8, _lib.ptr(out), st()),
+                   "pnr_gen_rays")
+        torch.cuda.synchronize()
+        yield "gen_rays pose rows %d" % rows, out.cpu()
+
+    # pnr_sample_fine: the surface-like cases, then test_sample_fine_up_to_1024's
+    def sample_fine(c):
+        B, kc, kf, kfd = c["zc"].shape[0], c["kc"], c["kf"], c["kfd"]
+        nf = kf - kfd
+        t = {k: up(c[k]) for k in ("rays", "zc", "w", "depth", "u", "uj", "nd")}
+        out = filled(B, kc + kf)
+        _lib.check(lib.pnr_sample_fine(_lib.ptr(t["rays"]), B, kc, _lib.ptr(t["zc"]), _lib.ptr(t["w"]),
+                                       _lib.ptr(t["depth"] if kfd > 0 else None), kf, kfd, ms.DEPTH_STD,
+                                       _lib.ptr(t["u"] if nf > 0 else None), _lib.ptr(t["uj"] if nf > 0 else None),
+                                       _lib.ptr(t["nd"] if kfd > 0 else None), int(c["lindisp"]), _lib.ptr(out), st()),
+                   "pnr_sample_fine")
+        torch.cuda.synchronize()
+        return out.cpu()
+
+    for case in ms.SAMPLER_CASES:
+        yield "sample_fine surface %s" % (case,), sample_fine(ms.sampler_inputs(*case))
+    mark = [m for m in tr.test_sample_fine_up_to_1024.pytestmark if m.name == "parametrize"][0]
+    for kc, kf, kfd, lindisp in mark.args[1]:
+        g = torch.Generator().manual_seed(kc + kf)   # the test's inputs (its draws are not moved off the cdf)
+        B = 65
+        rays = torch.cat([torch.randn(B, 6, generator=g), torch.full((B, 1), 0.5), torch.full((B, 1), 3.5)], 1)
+        zc = ref_cpu.sample_coarse(rays, kc, torch.rand(B, kc, generator=g), lindisp)
+        w = torch.rand(B, kc, generator=g) ** 4
+        w[:3] = 0.0
+        depth = 0.5 + 3.0 * torch.rand(B, generator=g)
+        u, uj = torch.rand(B, kf - kfd, generator=g), torch.rand(B, kf - kfd, generator=g)
+        nd = torch.randn(B, kfd, generator=g)
+        yield "sample_fine range %s" % ((kc, kf, kfd, lindisp),), sample_fine(
+            dict(rays=rays, zc=zc, w=w, depth=depth, u=u, uj=uj, nd=nd, kc=kc, kf=kf, kfd=kfd, lindisp=lindisp))
+
+    # pnr_composite_backward: every K, each optional gradient present and absent, on the module's inputs and
+    # on the opaque rows (with that module's output gradients)
+    for K in tb.BWD_K:
+        c = tb.composite_bwd_inputs(K, True)
+        rays, z, raw = ms.composite_rows(K, 100 + K)
+        rows = slice(0, ms.N_ROWS)
+        opaque = dict(c, rays=rays, z=z, raw=raw, d_rgb=c["d_rgb"][rows], d_depth=c["d_depth"][rows], d_w=c["d_w"][rows])
+        for what, cs in (("inputs", c), ("opaque rows", opaque)):
+            for use_depth, use_w, want_dz in ((1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0), (0, 0, 0)):
+                rc, d_raw, d_z = tb.run_composite_bwd(cs, bool(use_depth), bool(use_w), bool(want_dz), prefill=FILL)
+                _lib.check(rc, "pnr_composite_backward")
+                name = "composite_bwd %s K=%d d_depth=%d d_weights=%d d_z=%d" % (what, K, use_depth, use_w, want_dz)
+                yield name + " | d_raw", d_raw.cpu()
+                if d_z is not None:
+                    yield name + " | d_z", d_z.cpu()
+
+    # pnr_points_input_backward: d_z only (d_latent is summed with float atomics)
+    sd = synth.pixelnerf_state(5)
+    for cname, p in sorted(tb.INPUT_CASES.items()):
+        sn = tb.input_stage_scene(p["sb"], p["ns"], p["seed"])
+        rays, z = tb.input_stage_rays(sn, p["rpo"], p["K"], p["seed"] + 100)
+        n_points = p["sb"] * p["rpo"] * p["K"]
+        g = torch.Generator().manual_seed(p["seed"] + 200)
+        d_feat = up(torch.randn(p["ns"] * n_points, 64, generator=g))
+        d_zlat = up(torch.randn(p["ns"] * n_points, 512, generator=g))
+        net = PixelNeRFNet(tb.conf())
+        net.load_state_dict(sd, strict=False)
+        net = net.to(dev)
+        net.encode_latent(sn["latent"].to(dev), sn["poses"].to(dev), sn["focal"].to(dev), (tb.IMG_W, tb.IMG_H),
+                          c=sn["c"].to(dev), num_objs=sn["sb"])
+        desc, packed = net.mlp_coarse.packed(net.code, "fp32")
+        rays = up(rays.reshape(-1, 8))
+        z = up(z.reshape(rays.shape[0], p["K"]))
+        r = _lib.Rays(_lib.ptr(rays), rays.shape[0], p["rpo"])
+        mask = up(torch.from_numpy(synth.hash_uniform(31, n_points) < 0.4).to(torch.uint8))
+        for zm in (None, mask):
+            d_lat, d_z = torch.zeros_like(net.encoder.latent_cl), filled(n_points)
+            _lib.check(lib.pnr_points_input_backward_masked(
+                net.hip_scene(), desc, _lib.ptr(packed), r, _lib.ptr(z), p["K"], _lib.ptr(d_feat), _lib.ptr(d_zlat),
+                _lib.ptr(d_lat), _lib.ptr(d_z), _lib.ptr(zm), st()), "pnr_points_input_backward_masked")
+            torch.cuda.synchronize()
+            yield "points_input_bwd %s mask=%d | d_z" % (cname, zm is not None), d_z.cpu()
+
+    # renders whose fine pass runs the coarse MLP (the origin-carrying sort, z_new, k_merge_raw):
+    # 37 rays x (64 + 32) in march mode 0 with the coarse pack passed twice, then the 288-sample render of
+    # test_render_with_288_samples_per_ray[True]
+    net = tl.make_net("f16x3", True)
+    _encode(net, 1, 1)
+    rays = synth.scene_nmr(seed=3, n_rays=37)["rays"].to(dev).contiguous()
+    desc, pc = net.hip_mlp(True)
+    res = torchops.load().render_rays(*torchops.scene_args(net), torchops.desc_list(desc), pc, pc, net.hip_proj(True),
+                                      net.hip_proj(True), rays, 37, 64, 32, 0, 0.01, True, False, None, None, None,
+                                      None, 1234, 0, True, True, [], 0, None)
+    torch.cuda.synchronize()
+    for nm, x in zip(RENDER_OUT, res):
+        yield "render shared 37 x (64 + 32) mode 0 | %s" % nm, x.cpu()
+    kc, kf, kfd, B = 64, 224, 16, 13
+    sc = synth.scene_srn(seed=4, n_rays=B, pick="hash")
+    net = PixelNeRFNet(tgp.model_conf())
+    net.load_state_dict(synth.pixelnerf_state(3), strict=False)
+    net.mlp_precision = "f16x3"
+    net.mlp_fine = None
+    net = net.to(dev).eval()
+    net.encode_latent(sc["latent"].to(dev), sc["poses"].to(dev), sc["focal"].to(dev), (128, 128))
+    r = NeRFRenderer(n_coarse=kc, n_fine=kf, n_fine_depth=kfd, white_bkgd=True)
+    r.streams = synth.rng_streams(6, B, kc, kf, kfd)
+    r.return_z = True
+    with torch.no_grad():
+        out = r(net, sc["rays"][None].to(dev), want_weights=True)
+    torch.cuda.synchronize()
+    for pas in ("coarse", "fine"):
+        for k in ("rgb", "depth", "weights", "z"):
+            yield "render shared 288 samples | %s.%s" % (pas, k), getattr(getattr(out, pas), k).cpu()
+
+
+def save_march(out):
+    import torch
+
+    blob = dict(march_cases())
+    torch.save(blob, out)
+    print("saved", out, len(blob), "values", os.environ.get("PNR_LIB_PATH", "default"))
+
+
 def cmp(a, b):
     import torch
 
@@ -403,8 +593,60 @@ def time_cases(out, n_rays=8192, repeats=5):
         json.dump(res, f, indent=1)
 
 
+def time_march(out, n_rays=65536, warmup=3, launches=20):
+    import torch
+
+    from pnr import _lib
+
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(5)
+    res = {"lib": os.environ.get("PNR_LIB_PATH", "default"), "n_rays": n_rays, "cases": {}}
+
+    def timed(name, call):
+        ms = []
+        for i in range(warmup + launches):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(call(), name)
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                ms.append(e0.elapsed_time(e1))
+        res["cases"][name] = {"ms": ms, "median_ms": sorted(ms)[len(ms) // 2]}
+        print("%-28s median %.4f ms  min %.4f  max %.4f" % (name, res["cases"][name]["median_ms"], min(ms), max(ms)),
+              flush=True)
+
+    # (the backward at K = 256 too: k_composite_bwd<4> is the instantiation nearest a VGPR occupancy step)
+    for name, K in (("k_composite 65536 x 320", 320), ("k_composite_bwd 65536 x 96", 96),
+                    ("k_composite_bwd 65536 x 256", 256)):
+        near, far = 0.3, 4.0
+        rays = torch.cat([torch.randn(n_rays, 6, generator=g), torch.full((n_rays, 1), near),
+                          torch.full((n_rays, 1), far)], 1).to(dev)
+        z = torch.sort(near + (far - near) * torch.rand(n_rays, K, generator=g), -1)[0].to(dev)
+        raw = torch.rand(n_rays, K, 4, generator=g)
+        raw[..., 3] = torch.randn(n_rays, K, generator=g) * 4.0
+        raw = raw.to(dev)
+        st = _lib.stream_of(dev)
+        if K > 256:
+            w, rgb, d = (torch.empty(n_rays, K, device=dev), torch.empty(n_rays, 3, device=dev),
+                         torch.empty(n_rays, device=dev))
+            timed(name, lambda: lib.pnr_composite(_lib.ptr(z), _lib.ptr(raw), _lib.ptr(rays), n_rays, K, 1, _lib.ptr(w),
+                                                  _lib.ptr(rgb), _lib.ptr(d), st))
+        else:
+            d_rgb, d_depth = torch.randn(n_rays, 3, generator=g).to(dev), torch.randn(n_rays, generator=g).to(dev)
+            d_w = torch.randn(n_rays, K, generator=g).to(dev)
+            d_raw, d_z = torch.empty(n_rays, K, 4, device=dev), torch.empty(n_rays, K, device=dev)
+            timed(name, lambda: lib.pnr_composite_backward(_lib.ptr(z), _lib.ptr(raw), _lib.ptr(rays), n_rays, K, 1,
+                                                           _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w),
+                                                           _lib.ptr(d_raw), _lib.ptr(d_z), st))
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 if __name__ == "__main__":
     mode = sys.argv[1]
     if mode == "cmp":
         sys.exit(cmp(sys.argv[2], sys.argv[3]))
-    sys.exit({"save": save, "save-all": save_all, "save-train": save_train, "time": time_cases}[mode](sys.argv[2]))
+    sys.exit({"save": save, "save-all": save_all, "save-train": save_train, "save-march": save_march, "time": time_cases,
+              "time-march": time_march}[mode](sys.argv[2]))
