@@ -220,44 +220,65 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-class fused_march:
+class _restored:
+    """Context manager base: the library switch ``setter`` takes ``value`` inside and, after, the
+    value it held before (every ``pnr_*_set_*`` returns the previous one)."""
+    setter = None
+
+    def __enter__(self):
+        self.prev = getattr(load(), self.setter)(self.value)
+        return self
+
+    def __exit__(self, *exc):
+        getattr(load(), self.setter)(self.prev)
+        return False
+
+
+class fused_march(_restored):
     """Context manager: pnr_render_set_fused(mode) inside, the previous DEFAULT restored after
     (2, the default: fused passes + fine-draw kernel; 1: fine draws in the coarse epilogue too;
     0: the separate sample / composite kernels).  It changes the process default, which only
     calls without their own mode use; ``NeRFRenderer.march_mode`` names the mode per renderer
     (pnr_render_cfg.march_mode, no process state)."""
+    setter = "pnr_render_set_fused"
 
     def __init__(self, mode):
-        self.on = int(mode)
-
-    def __enter__(self):
-        self.prev = load().pnr_render_set_fused(self.on)
-        return self
-
-    def __exit__(self, *exc):
-        load().pnr_render_set_fused(self.prev)
-        return False
+        self.value = int(mode)
 
 
 # pnr_mlp_last_kernel (PNR_MLP_KERNEL_*)
 MLP_KERNEL_NONE, MLP_KERNEL_GENERAL, MLP_KERNEL_LEAN = 0, 1, 2
 
 
-class lean_mlp:
+class lean_mlp(_restored):
     """Context manager: pnr_mlp_set_lean(on) inside, the previous setting restored after.  Off,
     every point-model launch of the process takes the general kernel (bit-identical outputs)."""
+    setter = "pnr_mlp_set_lean"
 
     def __init__(self, on):
-        self.on = int(bool(on))
-
-    def __enter__(self):
-        self.prev = load().pnr_mlp_set_lean(self.on)
-        return self
-
-    def __exit__(self, *exc):
-        load().pnr_mlp_set_lean(self.prev)
-        return False
+        self.value = int(bool(on))
 
 
 def stream_of(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(name, device, *args):
+    """The one checked launch: ``name(*args, stream)`` of libpnr.so with ``device`` current and on
+    torch's current stream of that device; a non-zero status raises PnrError as ``check`` words it.
+    For every entry point that ends in a stream (the size queries, pnr_mlp_last_kernel, the set_*
+    switches and pnr_mc_case_table have none: ``load().pnr_x(...)``)."""
+    fn = getattr(load(), name)
+    with torch.cuda.device(device):
+        rc = fn(*args, stream_of(device))
+    if rc != 0:
+        check(rc, name)
+
+
+def workspace(nbytes, dtype, dev, refusal):
+    """The buffer a ``pnr_*_bytes`` size query sized, as a tensor of ``dtype`` on ``dev`` (``dev``
+    None: the check alone, no buffer).  A size of 0 is the library's refusal of the shape:
+    PnrError(``refusal``)."""
+    if nbytes == 0:
+        raise PnrError(refusal)
+    return None if dev is None else torch.empty(nbytes // dtype.itemsize, device=dev, dtype=dtype)

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import _lib
 from .consts import device_const
 from .prof import ranged
 
@@ -29,9 +30,16 @@ def _nhwc(maps):
     return all(t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous() for t in maps)
 
 
-def _latent_channels_last(maps):
-    from . import _lib
+def _map_tables(tensors, shapes):
+    """The host tables the channels-last kernels take for k maps: (pointers, channels, heights,
+    widths, k) from the maps' (or their gradients') tensors and their (n, C, h, w) shapes."""
+    k = len(tensors)
+    ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in tensors])
+    ch, hs, ws = ((ctypes.c_int32 * k)(*[s[i] for s in shapes]) for i in (1, 2, 3))
+    return ptrs, ch, hs, ws, k
 
+
+def _latent_channels_last(maps):
     maps = [t.float() for t in maps]
     nhwc = _nhwc(maps)
     if not nhwc:
@@ -39,14 +47,8 @@ def _latent_channels_last(maps):
     n, (h, w) = maps[0].shape[0], maps[0].shape[-2:]
     c_total = sum(t.shape[1] for t in maps)
     out = torch.empty(n, h, w, c_total, dtype=torch.float32, device=maps[0].device)
-    k = len(maps)
-    ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in maps])
-    ch = (ctypes.c_int32 * k)(*[t.shape[1] for t in maps])
-    hs = (ctypes.c_int32 * k)(*[t.shape[2] for t in maps])
-    ws = (ctypes.c_int32 * k)(*[t.shape[3] for t in maps])
-    name = "pnr_latent_channels_last_nhwc" if nhwc else "pnr_latent_channels_last"
-    _lib.check(getattr(_lib.load(), name)(ptrs, ch, hs, ws, k, n, _lib.ptr(out), h, w, _lib.stream_of(out.device)),
-               name)
+    _lib.call("pnr_latent_channels_last_nhwc" if nhwc else "pnr_latent_channels_last", out.device,
+              *_map_tables(maps, [t.shape for t in maps]), n, _lib.ptr(out), h, w)
     return out
 
 
@@ -67,20 +69,12 @@ class LatentChannelsLast(torch.autograd.Function):
         if g.is_cuda and ctx.nhwc and g.dtype == torch.float32:
             # channels-last maps (the trunk's layout): pnr_latent_channels_last_backward, one
             # deterministic gather launch for every map
-            from . import _lib
-
             g = g.contiguous()
             n, h, w = g.shape[:3]
             grads = [torch.empty(shp, dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
                      for shp in ctx.shapes]
-            k = len(grads)
-            ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in grads])
-            ch = (ctypes.c_int32 * k)(*[s[1] for s in ctx.shapes])
-            hs = (ctypes.c_int32 * k)(*[s[2] for s in ctx.shapes])
-            ws = (ctypes.c_int32 * k)(*[s[3] for s in ctx.shapes])
-            _lib.check(_lib.load().pnr_latent_channels_last_backward(
-                _lib.ptr(g), ptrs, ch, hs, ws, k, n, h, w, _lib.stream_of(g.device)),
-                "pnr_latent_channels_last_backward")
+            _lib.call("pnr_latent_channels_last_backward", g.device, _lib.ptr(g), *_map_tables(grads, ctx.shapes),
+                      n, h, w)
             return tuple(grads)
         gn = g.permute(0, 3, 1, 2)   # NCHW view of the channels-last gradient
         h, w = gn.shape[-2:]
@@ -203,10 +197,7 @@ class InferenceTrunk:
         self.key = key
 
     def fold(self):
-        from . import _lib
-
-        _lib.check(_lib.load().pnr_fold_batchnorm(self.table.data_ptr(), self.n_folds, self.max_elems,
-                                                  _lib.stream_of(self.device)), "pnr_fold_batchnorm")
+        _lib.call("pnr_fold_batchnorm", self.device, self.table.data_ptr(), self.n_folds, self.max_elems)
 
     # conv + bias + relu and conv + bias + residual + relu as MIOpen's fused forward ops
     # (torch.miopen_convolution_relu / _add_relu); False: F.conv2d + in-place relu / add.

@@ -19,15 +19,17 @@ import os
 import os.path as osp
 import warnings
 import weakref
+from collections import namedtuple
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, torchops
 from .consts import device_const
 from .conf import as_conf
 from .encoder import ImageEncoder, SpatialEncoder
+from .ops import _dev
 from .prof import ranged
 from .util import combine_interleaved, repeat_interleave
 
@@ -83,6 +85,14 @@ def module_params(mod, skip=None):
                 seen.add(id(p))
                 out.append(p)
     return out
+
+
+# One cached device buffer of a ResnetFC (the pack, the transposed pack, the projected latent):
+# ``owner`` a weak reference to the module that built it (see ResnetFC._cached), ``key`` the weight
+# version it was built from, ``buffers`` what the cache hands out, ``keep`` the temporaries the
+# stream-ordered launch read; the projection also names its ``latent`` (weak) and that tensor's
+# ``version``.
+_DeviceCache = namedtuple("_DeviceCache", "owner key buffers keep latent version", defaults=(None, None))
 
 
 class PositionalEncoding(nn.Module):
@@ -248,7 +258,19 @@ class ResnetFC(nn.Module):
         copy of the original's __dict__, so without the owner check a replica would find
         the original's packs, which live on the original's device (nerf.py:354-371)."""
         c = self.__dict__.get(name)
-        return c if c is not None and c[0]() is self else None
+        return c if c is not None and c.owner() is self else None
+
+    def _build(self, name, key, code, desc, nbytes, refusal, fn, lead, **latent):
+        """Build this module's entry of cache ``name`` under ``key`` and return its buffers ``(desc,
+        buf)``: ``buf`` is the fp32 buffer ``nbytes`` sizes (0: PnrError(``refusal``)) after the launch
+        ``fn(*lead(weights), buf, nbytes)``.  The launch is stream-ordered on the current stream: no
+        host sync (the temporaries stay referenced by the entry until the next build)."""
+        dev = self.lin_out.weight.device
+        buf = _lib.workspace(nbytes, torch.float32, dev, refusal)
+        w, keep = self._weights(code, desc)
+        _lib.call(fn, dev, *lead(w), _lib.ptr(buf), nbytes)
+        self.__dict__[name] = _DeviceCache(weakref.ref(self), key, (desc, buf), keep, **latent)
+        return desc, buf
 
     def _pack_key(self, code, precision):
         # the submodule list is cached (nn.Module.parameters() walks and de-duplicates the
@@ -267,25 +289,18 @@ class ResnetFC(nn.Module):
                                              for p in params + [code._freqs, code._phases])
 
     def packed(self, code, precision="fp32"):
-        """Packed fragment-order copy of the weights (re-packed when they change).  The
-        pack is stream-ordered on the current stream: no host sync (the temporaries stay
-        referenced by the cache until the next re-pack)."""
+        """``(desc, packed)``: the packed fragment-order copy of the weights (re-packed when they
+        change)."""
         key = self._pack_key(code, precision)
         cache = self._cached("_pnr_pack")
-        if cache is not None and cache[1] == key:
-            return cache[2], cache[3]
-        pe_n = int(code._freqs.numel())
-        desc = self.desc(pe_n, precision)
-        lib = _lib.load()
-        nbytes = lib.pnr_mlp_packed_bytes(desc)
-        if nbytes == 0:
-            _lib.check(-2, "pnr_mlp_packed_bytes")
-        dev = self.lin_out.weight.device
-        buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        w, keep = self._weights(code, desc)
-        _lib.check(lib.pnr_mlp_pack(w, _lib.ptr(buf), nbytes, _lib.stream_of(dev)), "pnr_mlp_pack")
-        self.__dict__["_pnr_pack"] = (weakref.ref(self), key, desc, buf, keep)
-        return desc, buf
+        if cache is not None and cache.key == key:
+            return cache.buffers
+        desc = self.desc(int(code._freqs.numel()), precision)
+        return self._build("_pnr_pack", key, code, desc, _lib.load().pnr_mlp_packed_bytes(desc),
+                           "pnr_mlp_packed_bytes: an MLP of d_in %d, d_latent %d, d_hidden %d, d_out %d, %d blocks, "
+                           "combine_layer %d, pe_n %d in %s not supported" % (
+                               desc.d_in, desc.d_latent, desc.d_hidden, desc.d_out, desc.n_blocks, desc.combine_layer,
+                               desc.pe_n, precision), "pnr_mlp_pack", lambda w: (w,))
 
     def packed_t(self, code, precision="f16x3"):
         """Transposed (backward) pack for pnr_mlp_backward, f16x3 only: (desc, packed,
@@ -293,19 +308,11 @@ class ResnetFC(nn.Module):
         desc, buf = self.packed(code, precision)
         key = self._pack_key(code, precision)
         cache = self._cached("_pnr_pack_t")
-        if cache is not None and cache[1] == key:
-            return desc, buf, cache[2]
-        lib = _lib.load()
-        nbytes = lib.pnr_mlp_packed_t_bytes(desc)
-        if nbytes == 0:
-            _lib.check(-2, "pnr_mlp_packed_t_bytes (f16x3 models only)")
-        dev = self.lin_out.weight.device
-        buf_t = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        w, keep = self._weights(code, desc)
-        _lib.check(lib.pnr_mlp_pack_t(w, _lib.ptr(buf), _lib.ptr(buf_t), nbytes, _lib.stream_of(dev)),
-                   "pnr_mlp_pack_t")
-        self.__dict__["_pnr_pack_t"] = (weakref.ref(self), key, buf_t, keep)
-        return desc, buf, buf_t
+        if cache is not None and cache.key == key:
+            return desc, buf, cache.buffers[1]
+        return desc, buf, self._build("_pnr_pack_t", key, code, desc, _lib.load().pnr_mlp_packed_t_bytes(desc),
+                                      "pnr_mlp_packed_t_bytes: no transposed pack in %s (f16x3 models only)" % precision,
+                                      "pnr_mlp_pack_t", lambda w: (w, _lib.ptr(buf)))[1]
 
     def latent_proj(self, code, scene, latent):
         """Projected latent of this MLP's lin_z layers for the encoded scene
@@ -317,23 +324,19 @@ class ResnetFC(nn.Module):
             return None
         key = self._pack_key(code, None)
         cache = self._cached("_pnr_proj")
-        if (cache is not None and cache[1] == key and cache[2]() is latent
-                and cache[3] == latent._version):
-            return cache[4]
+        if (cache is not None and cache.key == key and cache.latent() is latent
+                and cache.version == latent._version):
+            return cache.buffers[1]
         if latent.device != self.lin_out.weight.device:
             raise ValueError("pnr: latent on %s but the MLP weights on %s" % (latent.device,
                                                                               self.lin_out.weight.device))
         desc = self.desc(int(code._freqs.numel()))
-        lib = _lib.load()
-        nbytes = lib.pnr_latent_project_bytes(scene, desc)
-        if nbytes == 0:
-            _lib.check(-1, "pnr_latent_project_bytes")
-        buf = torch.empty(nbytes // 4, dtype=torch.float32, device=latent.device)
-        w, keep = self._weights(code, desc)
-        _lib.check(lib.pnr_latent_project(scene, w, _lib.ptr(buf), nbytes, _lib.stream_of(latent.device)),
-                   "pnr_latent_project")
-        self.__dict__["_pnr_proj"] = (weakref.ref(self), key, weakref.ref(latent), latent._version, buf, keep)
-        return buf
+        return self._build("_pnr_proj", key, code, desc, _lib.load().pnr_latent_project_bytes(scene, desc),
+                           "pnr_latent_project_bytes: a latent of %d x %d views, %d x %d x %d, for %d lin_z layers "
+                           "not supported" % (scene.n_obj, scene.n_views, scene.latent_h, scene.latent_w,
+                                              scene.latent_c, self.n_linz()),
+                           "pnr_latent_project", lambda w: (scene, w),
+                           latent=weakref.ref(latent), version=latent._version)[1]
 
     def drop_latent_proj(self):
         self.__dict__.pop("_pnr_proj", None)
@@ -557,35 +560,37 @@ class PixelNeRFNet(nn.Module):
         if r:
             raise NotImplementedError("pnr: " + r)
 
-    def hip_scene(self):
-        lat = self.encoder.latent_cl
-        sc = _lib.Scene()
-        sc.latent = lat.data_ptr()
-        sc.cams = self.cams.data_ptr()
-        sc.n_obj = self.num_objs
-        sc.n_views = self.num_views_per_obj
-        sc.latent_h, sc.latent_w, sc.latent_c = lat.shape[1], lat.shape[2], lat.shape[3]
+    def scene_fields(self):
+        """(latent_cl, cams, n_obj, n_views, image_w, image_h) of the encoded scene: what the torch
+        operators take (torchops.scene_args) and ``hip_scene`` puts into a pnr_scene."""
         wh = self.__dict__.get("_image_wh")
         if wh is None:   # image_shape installed without _set_cameras (e.g. a state dict)
             wh = (float(self.image_shape[0]), float(self.image_shape[1]))
-        sc.image_w, sc.image_h = wh
-        return sc
+        return (self.encoder.latent_cl, self.cams, int(self.num_objs), int(self.num_views_per_obj),
+                float(wh[0]), float(wh[1]))
+
+    def hip_scene(self):
+        lat, cams, n_obj, n_views, image_w, image_h = self.scene_fields()
+        return _lib.Scene(lat.data_ptr(), cams.data_ptr(), n_obj, n_views, lat.shape[1], lat.shape[2], lat.shape[3],
+                          image_w, image_h)
+
+    def pick_mlp(self, coarse):
+        """The MLP of a pass: the fine one falls back to the coarse one (mlp_fine of type empty)."""
+        return self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
 
     def hip_mlp(self, coarse):
-        mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
         if self.mlp_precision not in PRECISIONS:
             raise ValueError("mlp_precision must be one of %s" % sorted(PRECISIONS))
         self._check_f16()
-        return mlp.packed(self.code, self.mlp_precision)
+        return self.pick_mlp(coarse).packed(self.code, self.mlp_precision)
 
     def hip_proj(self, coarse, scene=None):
         """Device pointer-holder of the projected latent for the coarse / fine MLP, or None
         (use_latent_proj off, or no lin_z layers)."""
         if not self.use_latent_proj:
             return None
-        mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
-        return mlp.latent_proj(self.code, scene if scene is not None else self.hip_scene(),
-                               self.encoder.latent_cl)
+        return self.pick_mlp(coarse).latent_proj(self.code, scene if scene is not None else self.hip_scene(),
+                                                 self.encoder.latent_cl)
 
     def drop_latent_proj(self):
         """Forget the cached projections (they are rebuilt on the next render)."""
@@ -616,10 +621,6 @@ class PixelNeRFNet(nn.Module):
             if xyz.requires_grad or (viewdirs is not None and viewdirs.requires_grad):
                 return self._forward_torch(xyz, coarse, viewdirs)
             return self._forward_points_grad(xyz, coarse, viewdirs)
-        from .ops import _dev
-
-        from . import torchops
-
         xyz = _dev(xyz, "xyz")
         vd = _dev(viewdirs.reshape(SB, B, 3), "viewdirs") if viewdirs is not None else None
         desc, packed = self.hip_mlp(coarse)
@@ -632,8 +633,7 @@ class PixelNeRFNet(nn.Module):
         point, rays [xyz, viewdirs, 0, 0] at z = 0."""
         if self.mlp_precision == "f16":
             raise f16_refusal("a point query under autograd")
-        from .ops import _dev
-        from .train import RenderPoints, mlp_params
+        from .train import RenderPoints, mlp_params   # train imports this module
 
         SB, B, _ = xyz.shape
         xyz = _dev(xyz, "xyz").detach().float()
@@ -644,8 +644,7 @@ class PixelNeRFNet(nn.Module):
         lat = self.encoder.latent_cl
         if self.stop_encoder_grad:
             lat = lat.detach()
-        mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
-        raw = RenderPoints.apply(self, coarse, rays, z, lat, *mlp_params(mlp))
+        raw = RenderPoints.apply(self, coarse, rays, z, lat, *mlp_params(self.pick_mlp(coarse)))
         return raw.reshape(SB, B, 4)
 
     def _forward_torch(self, xyz, coarse, viewdirs):
@@ -687,8 +686,7 @@ class PixelNeRFNet(nn.Module):
             gl = self.global_encoder.latent
             gl = repeat_interleave(gl, mlp_input.shape[0] // gl.shape[0])
             mlp_input = torch.cat((gl, mlp_input), dim=-1)
-        mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
-        out = mlp(mlp_input, combine_inner_dims=(NS, B)).reshape(-1, B, self.d_out)
+        out = self.pick_mlp(coarse)(mlp_input, combine_inner_dims=(NS, B)).reshape(-1, B, self.d_out)
         return torch.cat((torch.sigmoid(out[..., :3]), torch.relu(out[..., 3:4])), dim=-1).reshape(SB, B, -1)
 
     # ---- checkpoints (models.py:268-316) -------------------------------------------

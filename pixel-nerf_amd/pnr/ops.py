@@ -3,20 +3,34 @@
 Each wrapper validates device / dtype / contiguity, allocates outputs with torch
 (the library never allocates), and launches on the current HIP stream.
 """
+import ctypes
+
 import torch
 
-from . import _lib
+from . import _lib, torchops, util
+from ._lib import call, ptr
+from ._lib import workspace as _workspace
 
 
-def _dev(t, name):
+def _typed(t, name, dtype):
+    """``t`` where it is a tensor of ``dtype`` on a HIP device; raises otherwise."""
     if not torch.is_tensor(t):
         raise TypeError("%s must be a tensor" % name)
     if t.device.type != "cuda":
         raise ValueError("pnr: %s must be on a HIP device (got %s); the HIP path has no CPU "
                          "fallback" % (name, t.device))
-    if t.dtype != torch.float32:
-        raise ValueError("pnr: %s must be float32 (got %s)" % (name, t.dtype))
-    return t.contiguous()
+    if t.dtype != dtype:
+        raise ValueError("pnr: %s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
+    return t
+
+
+def _dev(t, name):
+    return _typed(t, name, torch.float32).contiguous()
+
+
+def _host_floats(values, n):
+    """``values`` as a host ``float[n]`` (zero-filled past them), the void pointer the ABI takes."""
+    return ctypes.cast((ctypes.c_float * n)(*values), ctypes.c_void_p)
 
 
 def sample_coarse(rays, n_coarse, u_coarse, lindisp=False):
@@ -26,9 +40,7 @@ def sample_coarse(rays, n_coarse, u_coarse, lindisp=False):
     B = rays.shape[0]
     assert u.shape == (B, n_coarse), (u.shape, B, n_coarse)
     z = torch.empty(B, n_coarse, device=rays.device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.pnr_sample_coarse(_lib.ptr(rays), B, n_coarse, _lib.ptr(u), int(bool(lindisp)),
-                                     _lib.ptr(z), _lib.stream_of(rays.device)), "pnr_sample_coarse")
+    call("pnr_sample_coarse", rays.device, ptr(rays), B, n_coarse, ptr(u), int(bool(lindisp)), ptr(z))
     return z
 
 
@@ -46,11 +58,8 @@ def sample_fine(rays, z_coarse, coarse_weights, coarse_depth, n_fine, n_fine_dep
     uj = _dev(u_fine_jit, "u_fine_jit") if nf > 0 else None
     nd = _dev(n_depth, "n_depth") if n_fine_depth > 0 else None
     out = torch.empty(B, kc + n_fine, device=rays.device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.pnr_sample_fine(_lib.ptr(rays), B, kc, _lib.ptr(zc), _lib.ptr(w), _lib.ptr(d),
-                                   n_fine, n_fine_depth, float(depth_std), _lib.ptr(uf),
-                                   _lib.ptr(uj), _lib.ptr(nd), int(bool(lindisp)), _lib.ptr(out),
-                                   _lib.stream_of(rays.device)), "pnr_sample_fine")
+    call("pnr_sample_fine", rays.device, ptr(rays), B, kc, ptr(zc), ptr(w), ptr(d), n_fine, n_fine_depth,
+         float(depth_std), ptr(uf), ptr(uj), ptr(nd), int(bool(lindisp)), ptr(out))
     return out
 
 
@@ -59,8 +68,6 @@ def composite(z, raw, rays, white_bkgd, want_weights=True):
     z = _dev(z, "z")
     raw = _dev(raw, "raw")
     rays = _dev(rays, "rays")
-    from . import torchops
-
     B, K = z.shape
     assert raw.shape[:2] == (B, K) and raw.shape[-1] == 4, raw.shape
     w, rgb, depth = torchops.load().composite(z, raw, rays, bool(white_bkgd), bool(want_weights))
@@ -72,9 +79,7 @@ def rng_fill(seed, offset, stream, n_rays, width, device="cuda"):
     (n_rays, width) for rays offset .. offset + n_rays - 1, exactly as the render kernels
     draw them in counter mode.  stream: _lib.RNG_U_COARSE .. RNG_N_DEPTH."""
     out = torch.empty(n_rays, width, device=device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.pnr_rng_fill(int(seed), int(offset), int(stream), int(n_rays), int(width), _lib.ptr(out),
-                                _lib.stream_of(out.device)), "pnr_rng_fill")
+    call("pnr_rng_fill", out.device, int(seed), int(offset), int(stream), int(n_rays), int(width), ptr(out))
     return out
 
 
@@ -100,26 +105,19 @@ def marching_cubes(grid, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0))
     nx, ny, nz = (int(s) for s in grid.shape)
     if min(nx, ny, nz) < 1:
         raise ValueError("pnr: grid has an empty dimension %s" % (tuple(grid.shape),))
-    lib = _lib.load()
     dev = grid.device
-    nbytes = lib.pnr_mc_workspace_bytes(nx, ny, nz)
-    if nbytes == 0:
-        raise _lib.PnrError("pnr_mc_workspace_bytes: grid %s not supported (1 .. 1024 per axis)" % (
-            tuple(grid.shape),))
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    nbytes = _lib.load().pnr_mc_workspace_bytes(nx, ny, nz)
+    ws = _workspace(nbytes, torch.uint8, dev, "pnr_mc_workspace_bytes: grid %s not supported (1 .. 1024 per axis)" % (
+        tuple(grid.shape),))
     counts = torch.empty(2, device=dev, dtype=torch.int64)
-    st = _lib.stream_of(dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mc_count(_lib.ptr(grid), nx, ny, nz, float(level), _lib.ptr(ws), nbytes,
-                                    _lib.ptr(counts), st), "pnr_mc_count")
-        n_v, n_t = (int(c) for c in counts.cpu())
-        if n_v >= 2 ** 31 or n_t >= 2 ** 31:
-            raise _lib.PnrError("marching_cubes: %d vertices / %d faces do not fit int32 indices" % (n_v, n_t))
-        verts = torch.empty(n_v, 3, device=dev, dtype=torch.float32)
-        faces = torch.empty(n_t, 3, device=dev, dtype=torch.int32)
-        _lib.check(lib.pnr_mc_emit(_lib.ptr(grid), nx, ny, nz, float(level), _lib.ptr(ws), nbytes,
-                                   _lib.ptr(verts) if n_v else None, n_v, _lib.ptr(faces) if n_t else None, n_t,
-                                   st), "pnr_mc_emit")
+    call("pnr_mc_count", dev, ptr(grid), nx, ny, nz, float(level), ptr(ws), nbytes, ptr(counts))
+    n_v, n_t = (int(c) for c in counts.cpu())
+    if n_v >= 2 ** 31 or n_t >= 2 ** 31:
+        raise _lib.PnrError("marching_cubes: %d vertices / %d faces do not fit int32 indices" % (n_v, n_t))
+    verts = torch.empty(n_v, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(n_t, 3, device=dev, dtype=torch.int32)
+    call("pnr_mc_emit", dev, ptr(grid), nx, ny, nz, float(level), ptr(ws), nbytes, ptr(verts) if n_v else None, n_v,
+         ptr(faces) if n_t else None, n_t)
     if tuple(spacing) != (1.0, 1.0, 1.0) or tuple(origin) != (0.0, 0.0, 0.0):
         verts = verts * verts.new_tensor(spacing) + verts.new_tensor(origin)
     return verts, faces
@@ -156,18 +154,13 @@ def image_metrics(x, y, data_range=1.0, k1=0.01, k2=0.03):
         raise ValueError("pnr: x is %d x %d, smaller than the 7 x 7 SSIM window" % (h, w))
     if n < 1 or not 1 <= c <= 4:
         raise ValueError("pnr: x must hold at least one image of 1 .. 4 channels (got %s)" % (tuple(x.shape),))
-    lib = _lib.load()
     dev = x.device
-    nbytes = lib.pnr_image_metrics_workspace_bytes(n, h, w, c)
-    if nbytes == 0:
-        raise _lib.PnrError("pnr_image_metrics_workspace_bytes: shape %s not supported (H, W <= 8192, fewer "
-                            "than 2^24 tiles)" % (tuple(x.shape),))
-    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    nbytes = _lib.load().pnr_image_metrics_workspace_bytes(n, h, w, c)
+    ws = _workspace(nbytes, torch.float64, dev, "pnr_image_metrics_workspace_bytes: shape %s not supported (H, W <= "
+                    "8192, fewer than 2^24 tiles)" % (tuple(x.shape),))
     out = torch.empty(n, 2, device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_image_metrics(_lib.ptr(x), _lib.ptr(y), n, h, w, c, float(data_range), float(k1),
-                                         float(k2), _lib.ptr(ws), nbytes, _lib.ptr(out), _lib.stream_of(dev)),
-                   "pnr_image_metrics")
+    call("pnr_image_metrics", dev, ptr(x), ptr(y), n, h, w, c, float(data_range), float(k1), float(k2), ptr(ws),
+         nbytes, ptr(out))
     psnr = 10.0 * torch.log10(float(data_range) ** 2 / out[:, 0])
     return psnr, out[:, 1]
 
@@ -180,18 +173,6 @@ NEAREST_QUERIES = 1024
 NEAREST_TILE = 1024
 NEAREST_SLICE = 4096
 MESH_SCAN_CHUNK = 256
-
-
-def _typed(t, name, dtype):
-    """``t`` where it is a tensor of ``dtype`` on a HIP device; raises otherwise."""
-    if not torch.is_tensor(t):
-        raise TypeError("%s must be a tensor" % name)
-    if t.device.type != "cuda":
-        raise ValueError("pnr: %s must be on a HIP device (got %s); the HIP path has no CPU "
-                         "fallback" % (name, t.device))
-    if t.dtype != dtype:
-        raise ValueError("pnr: %s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
-    return t
 
 
 def _cloud(t, name, dtype=torch.float32):
@@ -228,14 +209,6 @@ def _seed(seed):
     return int(seed)
 
 
-def _workspace(nbytes, dtype, dev, refusal):
-    """The workspace a ``pnr_*_workspace_bytes`` call sized, as a tensor of ``dtype`` on ``dev``.  A
-    size of 0 is the library's refusal of the shape: PnrError(``refusal``)."""
-    if nbytes == 0:
-        raise _lib.PnrError(refusal)
-    return torch.empty(nbytes // dtype.itemsize, device=dev, dtype=dtype)
-
-
 def mesh_sample(verts, faces, n, seed=0, want_normals=True):
     """``n`` area-weighted samples of the surface of an indexed device mesh (include/pnr_abi.h,
     "Mesh metrics"; csrc/meshdist.hip): verts (V, 3) float32, faces (T, 3) int32 ->
@@ -247,19 +220,16 @@ def mesh_sample(verts, faces, n, seed=0, want_normals=True):
     if n < 1:
         raise ValueError("pnr: n must be >= 1 (got %d)" % n)
     seed = _seed(seed)
-    lib = _lib.load()
     dev = verts.device
-    nbytes = lib.pnr_mesh_sample_workspace_bytes(n_t) if n < 2 ** 31 else 0
+    nbytes = _lib.load().pnr_mesh_sample_workspace_bytes(n_t) if n < 2 ** 31 else 0
     ws = _workspace(nbytes, torch.float64, dev,
                     "pnr_mesh_sample: %d faces / %d samples not supported (below 2^31)" % (n_t, n))
     points = torch.empty(n, 3, device=dev, dtype=torch.float32)
     normals = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_normals else None
     tri = torch.empty(n, device=dev, dtype=torch.int32)
     area = torch.empty((), device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_sample(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, n, seed, _lib.ptr(ws), nbytes,
-                                       _lib.ptr(points), _lib.ptr(normals), _lib.ptr(tri), _lib.ptr(area),
-                                       _lib.stream_of(dev)), "pnr_mesh_sample")
+    call("pnr_mesh_sample", dev, ptr(verts), n_v, ptr(faces), n_t, n, seed, ptr(ws), nbytes, ptr(points), ptr(normals),
+         ptr(tri), ptr(area))
     return points, normals, tri, area
 
 
@@ -273,16 +243,13 @@ def nearest(a, b):
     n, m = int(a.shape[0]), int(b.shape[0])
     if n < 1 or m < 1:
         raise ValueError("pnr: a and b must hold at least one point each (got %d, %d)" % (n, m))
-    lib = _lib.load()
     dev = a.device
-    nbytes = lib.pnr_nearest_workspace_bytes(n, m)
+    nbytes = _lib.load().pnr_nearest_workspace_bytes(n, m)
     ws = _workspace(nbytes, torch.float32, dev, "pnr_nearest_workspace_bytes: %d x %d points not supported (n < 2^31, "
                     "m <= 65535 * %d)" % (n, m, NEAREST_SLICE))
     d2 = torch.empty(n, device=dev, dtype=torch.float32)
     idx = torch.empty(n, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_nearest(_lib.ptr(a), n, _lib.ptr(b), m, _lib.ptr(ws), nbytes, _lib.ptr(d2), _lib.ptr(idx),
-                                   _lib.stream_of(dev)), "pnr_nearest")
+    call("pnr_nearest", dev, ptr(a), n, ptr(b), m, ptr(ws), nbytes, ptr(d2), ptr(idx))
     return d2, idx
 
 
@@ -294,12 +261,8 @@ def mesh_distance_sums(d2_ab, idx_ab, d2_ba, idx_ba, na, nb, tau):
     """The eight float64 sums of pnr_mesh_distance_reduce as one device tensor (8,)."""
     dev = d2_ab.device
     out = torch.empty(8, device=dev, dtype=torch.float64)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_distance_reduce(_lib.ptr(d2_ab), _lib.ptr(idx_ab), int(d2_ab.shape[0]),
-                                                _lib.ptr(d2_ba), _lib.ptr(idx_ba), int(d2_ba.shape[0]), _lib.ptr(na),
-                                                _lib.ptr(nb), float(tau), _lib.ptr(out), _lib.stream_of(dev)),
-                   "pnr_mesh_distance_reduce")
+    call("pnr_mesh_distance_reduce", dev, ptr(d2_ab), ptr(idx_ab), int(d2_ab.shape[0]), ptr(d2_ba), ptr(idx_ba),
+         int(d2_ba.shape[0]), ptr(na), ptr(nb), float(tau), ptr(out))
     return out
 
 
@@ -365,15 +328,12 @@ def winding_number(verts, faces, points):
     n = int(points.shape[0])
     if n < 1:
         raise ValueError("pnr: points must hold at least one point (got %d)" % n)
-    lib = _lib.load()
     dev = verts.device
-    nbytes = lib.pnr_winding_workspace_bytes(n, n_t) if n_v < 2 ** 31 else 0
+    nbytes = _lib.load().pnr_winding_workspace_bytes(n, n_t) if n_v < 2 ** 31 else 0
     ws = _workspace(nbytes, torch.float64, dev, "pnr_winding_workspace_bytes: %d points x %d faces not supported "
                     "(n < 2^31, faces <= min(2^31 - 1, 65535 * %d))" % (n, n_t, WINDING_SLICE))
     w = torch.empty(n, device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_winding(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(points), n, _lib.ptr(ws), nbytes,
-                                   _lib.ptr(w), _lib.stream_of(dev)), "pnr_winding")
+    call("pnr_winding", dev, ptr(verts), n_v, ptr(faces), n_t, ptr(points), n, ptr(ws), nbytes, ptr(w))
     return w
 
 
@@ -387,8 +347,6 @@ def box_sample(lo, hi, n, seed=0, device="cuda"):
     """``n`` points uniform in the box [lo, hi] (two triples of floats) as a float32 device tensor
     (n, 3): pnr_box_sample (include/pnr_abi.h, "Mesh containment").  Sample s depends on (seed, s)
     only, so the first rows of a longer call equal a shorter one."""
-    import ctypes
-
     lo, hi = [float(x) for x in lo], [float(x) for x in hi]
     if len(lo) != 3 or len(hi) != 3:
         raise ValueError("pnr: lo and hi must be triples (got %d, %d values)" % (len(lo), len(hi)))
@@ -401,12 +359,8 @@ def box_sample(lo, hi, n, seed=0, device="cuda"):
         raise ValueError("pnr: box_sample draws on a HIP device (got %s); the HIP path has no CPU fallback" % (dev,))
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    c_lo, c_hi = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
     points = torch.empty(n, 3, device=dev, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_box_sample(ctypes.cast(c_lo, ctypes.c_void_p), ctypes.cast(c_hi, ctypes.c_void_p), n,
-                                      seed, _lib.ptr(points), _lib.stream_of(dev)), "pnr_box_sample")
+    call("pnr_box_sample", dev, _host_floats(lo, 3), _host_floats(hi, 3), n, seed, ptr(points))
     return points
 
 
@@ -419,11 +373,9 @@ RASTER_SMALL_PIXELS = 8
 RASTER_MAX_LIGHTS = 8
 
 
-def _raster_args(verts, faces, poses, width, height, focal, c):
-    """What mesh_raster and mesh_shade check and refuse alike; the last entry is the size of
-    mesh_raster's workspace."""
-    from . import util
-
+def _raster_args(verts, faces, poses, width, height, focal, c, want_ws):
+    """What mesh_raster and mesh_shade check and refuse alike; the last two entries are mesh_raster's
+    workspace (``want_ws``; mesh_shade takes none) and its size."""
     verts, faces, n_v, n_t = _mesh(verts, faces, "renders nothing")
     poses = _typed(poses, "poses", torch.float32)
     if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
@@ -437,11 +389,11 @@ def _raster_args(verts, faces, poses, width, height, focal, c):
     if width < 1 or height < 1:
         raise ValueError("pnr: width and height must be >= 1 (got %d, %d)" % (width, height))
     fx, fy, cx, cy = util._focal_c(width, height, focal, c)
-    nbytes = _lib.load().pnr_mesh_raster_workspace_bytes(nv, height, width, n_t)
-    if nbytes == 0 or n_v >= 2 ** 31:
-        raise _lib.PnrError("pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
-                            "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
-    return verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, nbytes
+    nbytes = _lib.load().pnr_mesh_raster_workspace_bytes(nv, height, width, n_t) if n_v < 2 ** 31 else 0
+    ws = _workspace(nbytes, torch.int64, verts.device if want_ws else None,
+                    "pnr_mesh_raster_workspace_bytes: %d views of %d x %d with %d faces not supported (sides "
+                    "in 1 .. 8192, NV H W and faces below 2^31)" % (nv, width, height, n_t))
+    return verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, ws, nbytes
 
 
 def mesh_raster(verts, faces, poses, width, height, focal, c=None):
@@ -452,35 +404,24 @@ def mesh_raster(verts, faces, poses, width, height, focal, c=None):
     ``util.gen_rays(poses, width, height, focal, ., ., c)``; ``face`` is -1 and ``depth`` 0 where the
     ray hits nothing, else ``depth`` is the distance along the unit direction (the composite's
     depth).  Both are functions of the inputs alone, bit for bit.  No host sync."""
-    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, nbytes = _raster_args(
-        verts, faces, poses, width, height, focal, c)
-    lib = _lib.load()
+    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, ws, nbytes = _raster_args(
+        verts, faces, poses, width, height, focal, c, True)
     dev = verts.device
-    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
     face = torch.empty(nv, height, width, device=dev, dtype=torch.int32)
     depth = torch.empty(nv, height, width, device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_raster(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(poses), nv,
-                                       int(poses.shape[1]), width, height, fx, fy, cx, cy, _lib.ptr(ws), nbytes,
-                                       _lib.ptr(face), _lib.ptr(depth), _lib.stream_of(dev)), "pnr_mesh_raster")
+    call("pnr_mesh_raster", dev, ptr(verts), n_v, ptr(faces), n_t, ptr(poses), nv, int(poses.shape[1]), width, height,
+         fx, fy, cx, cy, ptr(ws), nbytes, ptr(face), ptr(depth))
     return face, depth
 
 
-class raster_small_pixels:
+class raster_small_pixels(_lib._restored):
     """Context manager: pnr_mesh_raster_set_small(pixels) inside, the previous value restored after.
     It moves the threshold between the lane path and the wave path of ``mesh_raster`` (measurements
     and tests; the outputs do not depend on it)."""
+    setter = "pnr_mesh_raster_set_small"
 
     def __init__(self, pixels):
-        self.pixels = int(pixels)
-
-    def __enter__(self):
-        self.prev = _lib.load().pnr_mesh_raster_set_small(self.pixels)
-        return self
-
-    def __exit__(self, *exc):
-        _lib.load().pnr_mesh_raster_set_small(self.prev)
-        return False
+        self.value = int(pixels)
 
 
 def mesh_shade(verts, faces, poses, width, height, focal, face, depth, c=None, lights=(), weights=(),
@@ -490,10 +431,8 @@ def mesh_shade(verts, faces, poses, width, height, focal, face, depth, c=None, l
     ``want_normal`` the unit face normals turned towards the camera ``(NV, H, W, 3)`` (else None).
     ``lights``: up to RASTER_MAX_LIGHTS world positions (triples), ``weights`` one float each;
     ``albedo`` and ``background`` triples; colours of covered pixels are clamped to [0, 254/255]."""
-    import ctypes
-
-    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, _ = _raster_args(
-        verts, faces, poses, width, height, focal, c)
+    verts, faces, poses, nv, n_v, n_t, width, height, fx, fy, cx, cy, _, _ = _raster_args(
+        verts, faces, poses, width, height, focal, c, False)
     dev = verts.device
     for t, name, dtype in ((face, "face", torch.int32), (depth, "depth", torch.float32)):
         if tuple(_typed(t, name, dtype).shape) != (nv, height, width):
@@ -507,19 +446,14 @@ def mesh_shade(verts, faces, poses, width, height, focal, face, depth, c=None, l
     albedo, background = [float(x) for x in albedo], [float(x) for x in background]
     if len(albedo) != 3 or len(background) != 3:
         raise ValueError("pnr: albedo and background must be triples")
-    lib = _lib.load()
     n_l = len(lights)
-    c_l = (ctypes.c_float * max(1, 3 * n_l))(*[x for l in lights for x in l])
-    c_w = (ctypes.c_float * max(1, n_l))(*weights)
-    c_a, c_b = (ctypes.c_float * 3)(*albedo), (ctypes.c_float * 3)(*background)
+    face, depth = face.contiguous(), depth.contiguous()
     rgb = torch.empty(nv, height, width, 3, device=dev, dtype=torch.float32)
     normal = torch.empty(nv, height, width, 3, device=dev, dtype=torch.float32) if want_normal else None
-    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)   # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_shade(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(poses), nv,
-                                      int(poses.shape[1]), width, height, fx, fy, cx, cy, _lib.ptr(face.contiguous()),
-                                      _lib.ptr(depth.contiguous()), vp(c_l), vp(c_w), n_l, vp(c_a), float(ambient),
-                                      vp(c_b), _lib.ptr(rgb), _lib.ptr(normal), _lib.stream_of(dev)), "pnr_mesh_shade")
+    call("pnr_mesh_shade", dev, ptr(verts), n_v, ptr(faces), n_t, ptr(poses), nv, int(poses.shape[1]), width, height,
+         fx, fy, cx, cy, ptr(face), ptr(depth), _host_floats([x for l in lights for x in l], max(1, 3 * n_l)),
+         _host_floats(weights, max(1, n_l)), n_l, _host_floats(albedo, 3), float(ambient), _host_floats(background, 3),
+         ptr(rgb), ptr(normal))
     return rgb, normal
 
 
@@ -538,14 +472,11 @@ def mesh_weld_remap(verts):
     dev = verts.device
     if n_v == 0:
         return torch.empty(0, device=dev, dtype=torch.int32)
-    lib = _lib.load()
-    nbytes = lib.pnr_mesh_weld_workspace_bytes(n_v)
+    nbytes = _lib.load().pnr_mesh_weld_workspace_bytes(n_v)
     ws = _workspace(nbytes, torch.int32, dev,
                     "pnr_mesh_weld_workspace_bytes: %d vertices not supported (1 .. 2^29)" % n_v)
     remap = torch.empty(n_v, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_weld(_lib.ptr(verts), n_v, _lib.ptr(ws), nbytes, _lib.ptr(remap), _lib.stream_of(dev)),
-                   "pnr_mesh_weld")
+    call("pnr_mesh_weld", dev, ptr(verts), n_v, ptr(ws), nbytes, ptr(remap))
     return remap
 
 
@@ -588,19 +519,14 @@ def mesh_components(verts_or_n, faces, return_launches=False):
             raise ValueError("pnr: faces over an empty vertex set")
         out = (torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.int32), 0)
         return out + (0,) if return_launches else out
-    import ctypes
-
-    lib = _lib.load()
-    nbytes = lib.pnr_mesh_components_workspace_bytes(n_v, n_t)
+    nbytes = _lib.load().pnr_mesh_components_workspace_bytes(n_v, n_t)
     ws = _workspace(nbytes, torch.int32, dev, "pnr_mesh_components_workspace_bytes: %d vertices / %d faces not "
                     "supported (below 2^31)" % (n_v, n_t))
     vert_label = torch.empty(n_v, device=dev, dtype=torch.int32)
     face_label = torch.empty(n_t, device=dev, dtype=torch.int32)
     launches = ctypes.c_int32(0)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mesh_components(_lib.ptr(faces) if n_t else None, n_t, n_v, _lib.ptr(ws), nbytes,
-                                           _lib.ptr(vert_label), _lib.ptr(face_label) if n_t else None,
-                                           ctypes.byref(launches), _lib.stream_of(dev)), "pnr_mesh_components")
+    call("pnr_mesh_components", dev, ptr(faces) if n_t else None, n_t, n_v, ptr(ws), nbytes, ptr(vert_label),
+         ptr(face_label) if n_t else None, ctypes.byref(launches))
     n_c = int((vert_label == torch.arange(n_v, device=dev, dtype=torch.int32)).sum())
     out = (vert_label, face_label, n_c)
     return out + (int(launches.value),) if return_launches else out
@@ -631,10 +557,6 @@ def mesh_component_stats(verts, faces, vert_label, face_label):
         order = torch.sort(face_id, stable=True).indices.contiguous()
         seg = torch.zeros(n_c + 1, device=dev, dtype=torch.int64)
         seg[1:] = torch.cumsum(cnt_f, 0)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(lib.pnr_mesh_component_sums(_lib.ptr(verts), n_v, _lib.ptr(faces), n_t, _lib.ptr(order),
-                                                   _lib.ptr(seg), n_c, _lib.ptr(sums), _lib.stream_of(dev)),
-                       "pnr_mesh_component_sums")
+        call("pnr_mesh_component_sums", dev, ptr(verts), n_v, ptr(faces), n_t, ptr(order), ptr(seg), n_c, ptr(sums))
     return {"labels": labels, "vert_id": vert_id, "face_id": face_id, "n_verts": cnt_v, "n_faces": cnt_f,
             "area": sums[:, 0].contiguous(), "signed_volume": sums[:, 1].contiguous()}

@@ -22,9 +22,11 @@ model-callback and training paths always draw with torch in the reference's orde
 """
 import torch
 
-from . import _lib, ops
-from .prof import ranged
+from . import ops, torchops
 from .conf import as_conf
+from .models import PixelNeRFNet, f16_refusal
+from .prof import ranged
+from .train import Composite, FinePass, RenderPoints, mlp_params
 
 __all__ = ["NeRFRenderer", "DotMap"]
 
@@ -178,6 +180,40 @@ class NeRFRenderer(torch.nn.Module):
                 n_d = torch.randn(n_rays, kfd, device=device)
         return u_c, u_f, u_j, n_d
 
+    def _draw_fine(self, B, dev):
+        """(u_fine, u_fine_jit, n_depth) drawn after the coarse pass: with training-mode sigma noise
+        the reference's draws interleave with the noise draws (u_coarse, coarse noise, these three,
+        fine noise)."""
+        nf, kfd = self.fine_counts()
+        empty = torch.zeros(B, 0, device=dev)
+        u_f = torch.rand(B, nf, device=dev) if nf > 0 else empty
+        u_j = torch.rand(B, nf, device=dev) if nf > 0 else empty
+        n_d = torch.randn(B, kfd, device=dev) if kfd > 0 else empty
+        return u_f, u_j, n_d
+
+    def _fine_depths(self, rays, z_c, w_c, depth_c, u_f, u_j, n_d):
+        """The fine pass's depths as the reference's autograd graph builds them (nerf.py:284-295):
+        importance samples from the detached coarse weights under no_grad (nerf.py:130), depth
+        samples that keep their gradient to the coarse depth, clamped to near and far
+        (nerf.py:150-161), one torch.sort over [coarse + importance, depth].  Returns (sorted
+        depths (B, K) contiguous, the sort's permutation, the number of coarse + importance
+        columns: an entry of the permutation at or past it is a depth sample)."""
+        nf, kfd = self.fine_counts()
+        with torch.no_grad():
+            z_ci = (ops.sample_fine(rays, z_c, w_c.detach(), depth_c.detach(), nf, 0, self.depth_std, u_f, u_j,
+                                    None, self.lindisp) if nf > 0 else z_c)
+        parts = [z_ci]
+        if kfd > 0:
+            z_d = depth_c.unsqueeze(1).repeat((1, kfd)) + n_d * self.depth_std
+            parts.append(torch.max(torch.min(z_d, rays[:, -1:]), rays[:, -2:-1]))
+        z_f, order = torch.sort(torch.cat(parts, -1), -1)
+        return z_f.contiguous(), order, z_ci.shape[1]
+
+    @staticmethod
+    def _require_hip_rays(rays):
+        if rays.device.type != "cuda":
+            raise ValueError("pnr: rays must be on the HIP device")
+
     # ---- building blocks (HIP) -------------------------------------------------------
     def sample_coarse(self, rays, u=None):
         if u is None:
@@ -212,9 +248,7 @@ class NeRFRenderer(torch.nn.Module):
             out = torch.cat([out[..., :3], out[..., 3:4] + (n * self.noise_std).unsqueeze(-1), out[..., 4:]], -1)
         raw = out[..., :4].contiguous()
         if torch.is_grad_enabled() and (raw.requires_grad or z_samp.requires_grad):
-            from .train import Composite   # the composite kernel with its backward kernel
-
-            return Composite.apply(z_samp, raw, rays, self.white_bkgd)
+            return Composite.apply(z_samp, raw, rays, self.white_bkgd)   # the composite kernel with its backward
         return ops.composite(z_samp, raw, rays, self.white_bkgd)
 
     # ---- forward (nerf.py:251-303) ---------------------------------------------------
@@ -227,8 +261,6 @@ class NeRFRenderer(torch.nn.Module):
         sb = rays.shape[0]
         rays = rays.reshape(-1, 8).contiguous()
         B = rays.shape[0]
-        from .models import PixelNeRFNet
-
         if isinstance(model, PixelNeRFNet) and model.fused_conf_reason() is None:
             # the sigma noise of training mode (nerf.py:225-226) is added between the model
             # and the composite, which the fused march does not expose: the training
@@ -248,20 +280,13 @@ class NeRFRenderer(torch.nn.Module):
         With noise_std > 0 in training mode, sigma noise is added before compositing
         (nerf.py:225-226) and the draws follow the reference's order: u_coarse, coarse
         noise, u_fine, u_fine_jit, n_depth, fine noise."""
-        from .train import Composite, FinePass, RenderPoints, mlp_params
-
         if net.mlp_precision == "f16":
-            from .models import f16_refusal
-
             raise f16_refusal("a render under autograd or with training-mode sigma noise")
         r = net.hip_unsupported_reason()
         if r:
             raise NotImplementedError("pnr: " + r)
-        if rays.device.type != "cuda":
-            raise ValueError("pnr: rays must be on the HIP device")
+        self._require_hip_rays(rays)
         kc = self.n_coarse
-        nf, kfd = self.fine_counts()
-        kf = nf + kfd
         noisy = self.training and self.noise_std > 0.0
         B, dev = rays.shape[0], rays.device
         lazy = noisy and self.streams is None   # draws interleave with the noise draws
@@ -286,22 +311,11 @@ class NeRFRenderer(torch.nn.Module):
         outputs = DotMap(coarse=self._pack_out(w_c, rgb_c, d_c, sb, want_weights, z_c))
         if self.using_fine:
             if lazy:
-                empty = torch.zeros(B, 0, device=dev)
-                u_f = torch.rand(B, nf, device=dev) if nf > 0 else empty
-                u_j = torch.rand(B, nf, device=dev) if nf > 0 else empty
-                n_d = torch.randn(B, kfd, device=dev) if kfd > 0 else empty
-            with torch.no_grad():
-                z_ci = (ops.sample_fine(rays, z_c, w_c.detach(), d_c.detach(), nf, 0, self.depth_std, u_f, u_j,
-                                        None, self.lindisp) if nf > 0 else z_c)
-            parts = [z_ci]
-            if kfd > 0:
-                z_d = d_c.unsqueeze(1).repeat((1, kfd)) + n_d * self.depth_std
-                parts.append(torch.max(torch.min(z_d, rays[:, -1:]), rays[:, -2:-1]))
-            z_f, order = torch.sort(torch.cat(parts, -1), -1)
-            z_f = z_f.contiguous()
+                u_f, u_j, n_d = self._draw_fine(B, dev)
+            z_f, order, n_imp = self._fine_depths(rays, z_c, w_c, d_c, u_f, u_j, n_d)
             # only the depth samples' dL/dz reaches the graph (the importance samples carry none)
-            fine = FinePass(order >= z_ci.shape[1] if kfd > 0 else None)
-            p_f = mlp_params(net.mlp_fine) if net.mlp_fine is not None else p_c
+            fine = FinePass(order >= n_imp if n_imp < z_f.shape[1] else None)
+            p_f = mlp_params(net.pick_mlp(False))
             raw_f = add_noise(RenderPoints.apply(net, fine, rays, z_f, lat, *p_f))
             w_f, rgb_f, d_f = Composite.apply(z_f, raw_f.contiguous(), rays, self.white_bkgd)
             outputs.fine = self._pack_out(w_f, rgb_f, d_f, sb, want_weights, z_f)
@@ -321,8 +335,7 @@ class NeRFRenderer(torch.nn.Module):
         fine MLP over the coarse samples (nerf.py:284-298 with all_samps = [z_coarse]): a
         second coarse-only march with the fine model and the same draws."""
         net._require_hip()
-        if rays.device.type != "cuda":
-            raise ValueError("pnr: rays must be on the HIP device")
+        self._require_hip_rays(rays)
         B = rays.shape[0]
         kc = self.n_coarse
         nf, kfd = self.fine_counts()
@@ -362,10 +375,10 @@ class NeRFRenderer(torch.nn.Module):
         """One torch.ops.pnr.render_rays call (pnr_render_forward_proj).  coarse=False: the
         fine MLP in the coarse slot (a coarse-only march with the fine model).  ``order``: the
         processing order (pnr_render_cfg.ray_order) or None."""
-        from . import torchops
-
         ops_ = torchops.load()
         B = rays.shape[0]
+        # without fine samples the fine slot is not run: it gets the coarse slot's pack and no projection
+        # (which MLP a slot with samples runs is pick_mlp's decision, inside hip_mlp / hip_proj)
         desc, pc = net.hip_mlp(coarse)
         pf = net.hip_mlp(False)[1] if kf > 0 else pc
         zc = net.hip_proj(coarse)
@@ -419,19 +432,11 @@ class NeRFRenderer(torch.nn.Module):
         outputs = DotMap(coarse=self._pack_out(w_c, rgb_c, depth_c, sb, want_weights, z_c))
         if self.using_fine:
             if lazy:
-                empty = torch.zeros(B, 0, device=dev)
-                u_f = torch.rand(B, nf, device=dev) if nf > 0 else empty
-                u_j = torch.rand(B, nf, device=dev) if nf > 0 else empty
-                n_d = torch.randn(B, kfd, device=dev) if kfd > 0 else empty
+                u_f, u_j, n_d = self._draw_fine(B, dev)
             if nf + kfd == 0:
                 z_f = z_c
             elif torch.is_grad_enabled() and kfd > 0 and depth_c.requires_grad:
-                with torch.no_grad():
-                    z_ci = (ops.sample_fine(rays, z_c, w_c.detach(), depth_c.detach(), nf, 0, self.depth_std, u_f,
-                                            u_j, None, self.lindisp) if nf > 0 else z_c)
-                z_d = depth_c.unsqueeze(1).repeat((1, kfd)) + n_d * self.depth_std
-                z_d = torch.max(torch.min(z_d, rays[:, -1:]), rays[:, -2:-1])
-                z_f = torch.sort(torch.cat([z_ci, z_d], -1), -1)[0].contiguous()
+                z_f = self._fine_depths(rays, z_c, w_c, depth_c, u_f, u_j, n_d)[0]
             else:
                 z_f = ops.sample_fine(rays, z_c, w_c.detach(), depth_c.detach(), nf + kfd, kfd, self.depth_std,
                                       u_f, u_j, n_d, self.lindisp)

@@ -41,6 +41,4 @@ def desc_list(desc):
 
 def scene_args(net):
     """(latent_cl, cams, n_obj, n_views, image_w, image_h) of an encoded PixelNeRFNet."""
-    sc = net.hip_scene()
-    return (net.encoder.latent_cl, net.cams, int(sc.n_obj), int(sc.n_views), float(sc.image_w),
-            float(sc.image_h))
+    return net.scene_fields()

@@ -29,9 +29,13 @@ util.py:461-471) and the input-stage backward scatters into each view's latent. 
 f16x3 backward chain (``pnr_mlp_backward_views``) covers any number of views; the fp32 / bf16
 arithmetics run the ResnetFC backward as per-layer GEMMs (``mlp_backward``).
 """
+import ctypes
+
 import torch
 
 from . import _lib, ops
+from ._lib import call, ptr
+from .models import f16_refusal, module_params
 
 __all__ = ["RenderPoints", "Composite", "mlp_backward", "mlp_backward_fused", "weight_grad", "mlp_params"]
 
@@ -59,8 +63,6 @@ def _ev_end(name, e0, flop):
 def mlp_params(mlp):
     """The ResnetFC parameters in registration order (what autograd tracks), also on an
     nn.DataParallel replica (bind_parallel, nerf.py:354-371)."""
-    from .models import module_params
-
     return module_params(mlp)
 
 
@@ -178,16 +180,13 @@ def weight_grad(dys, xs, P, arith="f16x3"):
     split products with running per-(chunk, channel) scales, fp32-level error relative to the
     channel scale (include/pnr_abi.h states the bound); "bf16x6" (k_wgrad): split-bf16 products,
     fp32-level error per element whatever the dynamic range."""
-    import ctypes
-
     n = len(dys)
     dev = dys[0].device
     out = torch.empty(n, 512, 512, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    wsb = lib.pnr_weight_grad_workspace_bytes(n, P)
-    if wsb == 0 and P > 0:
-        _lib.check(-1, "pnr_weight_grad_workspace_bytes")
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    wsb = _lib.load().pnr_weight_grad_workspace_bytes(n, P)
+    # no rows need no workspace (a size of 0 is no refusal then): one byte, for a pointer to pass
+    ws = _lib.workspace(wsb or int(P <= 0), torch.uint8, dev,
+                        "pnr_weight_grad_workspace_bytes: %d layers of %d rows not supported (1 .. 16 layers)" % (n, P))
 
     def arr(ts):
         for t in ts:
@@ -196,8 +195,7 @@ def weight_grad(dys, xs, P, arith="f16x3"):
 
     outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
     e0 = _ev_begin()
-    _lib.check(lib.pnr_weight_grad_arith(arr(dys), arr(xs), outs, n, P, _lib.WGRAD_ARITH[arith], _lib.ptr(ws),
-                                         wsb, _lib.stream_of(dev)), "pnr_weight_grad_arith")
+    call("pnr_weight_grad_arith", dev, arr(dys), arr(xs), outs, n, P, _lib.WGRAD_ARITH[arith], ptr(ws), wsb)
     _ev_end("weight_grad", e0, 2.0 * 512 * 512 * n * P)
     return out
 
@@ -240,14 +238,11 @@ def mlp_backward_fused(mlp, code, precision, save, d_o, P, ns=1, wgrad_arith="f1
     dzl = torch.empty(R, 512, dtype=torch.float32, device=dev) if lin_z else None
     w_out = mlp.lin_out.weight.detach().float().contiguous()
     sums = torch.empty(2 * nb + 1, 512, dtype=torch.float32, device=dev)   # bias gradients, dy's slot order
-    lib = _lib.load()
-    wsb = lib.pnr_mlp_backward_workspace_bytes(desc, P)
+    wsb = _lib.load().pnr_mlp_backward_workspace_bytes(desc, P)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
     e0 = _ev_begin()
-    _lib.check(lib.pnr_mlp_backward_views(desc, _lib.ptr(packed), _lib.ptr(packed_t), _lib.ptr(w_out),
-                                          _lib.ptr(save), _lib.ptr(d_o), P, ns, _lib.ptr(dy), _lib.ptr(dzl),
-                                          _lib.ptr(sums), _lib.ptr(ws), wsb, _lib.stream_of(dev)),
-               "pnr_mlp_backward_views")
+    call("pnr_mlp_backward_views", dev, desc, ptr(packed), ptr(packed_t), ptr(w_out), ptr(save), ptr(d_o), P, ns,
+         ptr(dy), ptr(dzl), ptr(sums), ptr(ws), wsb)
     _ev_end("mlp_backward", e0, backward_chain_flop(mlp, P, ns))
     g = {}
     xf = slot(2 * nb, P)
@@ -299,15 +294,12 @@ class RenderPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, coarse, rays, z, latent_cl, *params):
         if net.mlp_precision == "f16":
-            from .models import f16_refusal
-
             raise f16_refusal("train.RenderPoints, the training forward")
-        mlp = net.mlp_coarse if (coarse or net.mlp_fine is None) else net.mlp_fine
+        mlp = net.pick_mlp(coarse)
         desc, packed = mlp.packed(net.code, net.mlp_precision)
         sc = net.hip_scene()
         B, K = z.shape
         P = B * K
-        lib = _lib.load()
         dev = z.device
         _on_device(dev, "packed rays latent cams", packed, rays, net.encoder.latent_cl, net.cams)
         ns = net.num_views_per_obj
@@ -315,17 +307,15 @@ class RenderPoints(torch.autograd.Function):
         # no activation save without a backward (no_grad); callers driving forward() by hand
         # (tests) pass a plain namespace and always get the save
         if any(getattr(ctx, "needs_input_grad", (True,))):
-            n_save = lib.pnr_point_save_floats(desc, P * ns)
-            if n_save == 0:
-                _lib.check(-1, "pnr_point_save_floats")
-            save = torch.empty(n_save, dtype=torch.float32, device=dev)
-        ws_bytes = lib.pnr_point_query_workspace_bytes(sc, P)
+            save = _lib.workspace(4 * _lib.load().pnr_point_save_floats(desc, P * ns), torch.float32, dev,
+                                  "pnr_point_save_floats: no activation save for %d points x %d views of this MLP"
+                                  % (P, ns))
+        ws_bytes = _lib.load().pnr_point_query_workspace_bytes(sc, P)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
         out = torch.empty(P, 4, dtype=torch.float32, device=dev)
         e0 = _ev_begin()
-        _lib.check(lib.pnr_render_points(sc, desc, _lib.ptr(packed), _rays_of(net, rays, B), _lib.ptr(z), K, _lib.ptr(out),
-                                         _lib.ptr(save), _lib.ptr(ws), ws_bytes, _lib.stream_of(dev)),
-                   "pnr_render_points")
+        call("pnr_render_points", dev, sc, desc, ptr(packed), _rays_of(net, rays, B), ptr(z), K, ptr(out), ptr(save),
+             ptr(ws), ws_bytes)
         _ev_end("forward", e0, forward_flop(mlp, P, ns))
         ctx.save_for_backward(rays, z, out, save, latent_cl)
         ctx.net, ctx.mlp, ctx.desc, ctx.packed, ctx.params = net, mlp, desc, packed, params
@@ -354,17 +344,15 @@ class RenderPoints(torch.autograd.Function):
         if need_z or need_lat:
             if d_zlat is None:
                 d_zlat = torch.zeros(ns * P, 512, dtype=torch.float32, device=z.device)
-            lib = _lib.load()
             _on_device(z.device, "packed rays d_feat d_zlat d_latent cams latent", ctx.packed, rays, d_feat,
                        d_zlat, d_lat, net.cams, net.encoder.latent_cl)
             zm = getattr(ctx, "z_mask", None)
             if zm is not None:
                 zm = zm.reshape(P).to(device=z.device, dtype=torch.uint8).contiguous()
-            _lib.check(lib.pnr_points_input_backward_masked(
-                net.hip_scene(), ctx.desc, _lib.ptr(ctx.packed), _rays_of(net, rays, B), _lib.ptr(z), K,
-                _lib.ptr(d_feat.contiguous()),
-                _lib.ptr(d_zlat.contiguous()), _lib.ptr(d_lat), _lib.ptr(d_z), _lib.ptr(zm) if need_z else None,
-                _lib.stream_of(z.device)), "pnr_points_input_backward_masked")
+            d_feat, d_zlat = d_feat.contiguous(), d_zlat.contiguous()
+            call("pnr_points_input_backward_masked", z.device, net.hip_scene(), ctx.desc, ptr(ctx.packed),
+                 _rays_of(net, rays, B), ptr(z), K, ptr(d_feat), ptr(d_zlat), ptr(d_lat), ptr(d_z),
+                 ptr(zm) if need_z else None)
         grads = [g.get(p) for p in ctx.params]
         return (None, None, None, d_z.view(B, K) if need_z else None, d_lat, *grads)
 
@@ -388,10 +376,7 @@ class Composite(torch.autograd.Function):
         d_raw = torch.empty(B, K, 4, dtype=torch.float32, device=z.device)
         d_z = torch.empty(B, K, dtype=torch.float32, device=z.device) if ctx.needs_input_grad[0] else None
         _on_device(z.device, "raw rays d_rgb d_depth d_weights", raw, rays, d_rgb, d_depth, d_w)
-        lib = _lib.load()
-        _lib.check(lib.pnr_composite_backward(
-            _lib.ptr(z), _lib.ptr(raw), _lib.ptr(rays), B, K, int(bool(ctx.white_bkgd)),
-            _lib.ptr(d_rgb.contiguous()), _lib.ptr(d_depth.contiguous() if d_depth is not None else None),
-            _lib.ptr(d_w.contiguous() if d_w is not None else None), _lib.ptr(d_raw), _lib.ptr(d_z),
-            _lib.stream_of(z.device)), "pnr_composite_backward")
+        d_rgb, d_depth, d_w = (None if t is None else t.contiguous() for t in (d_rgb, d_depth, d_w))
+        call("pnr_composite_backward", z.device, ptr(z), ptr(raw), ptr(rays), B, K, int(bool(ctx.white_bkgd)),
+             ptr(d_rgb), ptr(d_depth), ptr(d_w), ptr(d_raw), ptr(d_z))
         return d_z, d_raw, None, None

@@ -26,6 +26,8 @@ import math
 import numpy as np
 import torch
 
+from . import _lib
+
 __all__ = [
     "repeat_interleave",
     "combine_interleaved",
@@ -142,15 +144,12 @@ def gen_rays(poses, width, height, focal, z_near, z_far, c=None, ndc=False):
     if ndc:
         raise NotImplementedError("gen_rays(ndc=True): the reference defines no ndc_rays (util.py:262)")
     if poses.is_cuda:
-        from . import _lib
-
         fx, fy, cx, cy = _focal_c(width, height, focal, c)
         p = poses.detach().to(torch.float32).contiguous()
         rows = p.shape[-2]
         out = torch.empty(p.shape[0], height, width, 8, dtype=torch.float32, device=p.device)
-        _lib.check(_lib.load().pnr_gen_rays(_lib.ptr(p), p.shape[0], rows, width, height, fx, fy, cx,
-                                            cy, float(z_near), float(z_far), _lib.ptr(out),
-                                            _lib.stream_of(p.device)), "pnr_gen_rays")
+        _lib.call("pnr_gen_rays", p.device, _lib.ptr(p), p.shape[0], rows, width, height, fx, fy, cx, cy,
+                  float(z_near), float(z_far), _lib.ptr(out))
         return out
     nv = poses.shape[0]
     device = poses.device

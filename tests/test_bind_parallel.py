@@ -11,6 +11,8 @@ with CPU clones instead of the cross-device broadcast, and ``_fake_lib`` stands 
 packing entry points so the cache logic runs without a GPU.  The GPU test of the real
 nn.DataParallel path is tests/test_gpu_parity.py::test_bind_parallel_replicas_render_fixture.
 """
+import contextlib
+import weakref
 from collections import OrderedDict
 
 import pytest
@@ -84,6 +86,7 @@ def fake_lib(monkeypatch):
     fake = _FakeLib()
     monkeypatch.setattr(_lib, "load", lambda: fake)
     monkeypatch.setattr(_lib, "stream_of", lambda dev: None)
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())   # _lib.call's device guard
     return fake
 
 
@@ -105,7 +108,7 @@ def test_replica_packs_its_own_weights(fake_lib):
         rep = emulate_replicate(net)
         rm = rep.mlp_coarse
         # the replica inherited the original's caches in its __dict__ copy ...
-        assert rm.__dict__["_pnr_pack"][3] is buf and rm.__dict__["_pnr_mods"][0][0] is m
+        assert rm.__dict__["_pnr_pack"].buffers[1] is buf and rm.__dict__["_pnr_mods"][0][0] is m
         # ... but neither is its own: the key is built from the replica's parameters, and the
         # pack it returns is one it built
         k_rep = rm._pack_key(rep.code, "f16x3")
@@ -113,7 +116,7 @@ def test_replica_packs_its_own_weights(fake_lib):
         assert rm.__dict__["_pnr_mods"][0][0] is rm
         _, rbuf = rm.packed(rep.code, "f16x3")
         assert rbuf is not buf and fake_lib.packs == 2
-        assert rm.__dict__["_pnr_pack"][0]() is rm
+        assert rm.__dict__["_pnr_pack"].owner() is rm
         assert rm.packed(rep.code, "f16x3")[1] is rbuf and fake_lib.packs == 2   # its own cache hits
         # the original still has its own pack
         assert m.packed(net.code, "f16x3")[1] is buf and fake_lib.packs == 2
@@ -128,6 +131,63 @@ def test_replica_projects_its_own_latent(fake_lib):
         p1 = rep.hip_proj(True)
         assert p1 is not p0 and fake_lib.projs == 2
         assert rep.hip_proj(True) is p1 and fake_lib.projs == 2
+
+
+def test_cache_records_are_refused_by_a_module_that_is_not_their_owner(fake_lib, monkeypatch):
+    """The pack, the transposed pack and the projection are one record type whose ``owner`` is the
+    module that built it: ``_cached`` hands a record to that module only, so a replica (which
+    inherits all three in its __dict__ copy) and a module the records were copied into by hand
+    build their own, and the original keeps its."""
+    fake_lib.packs_t = 0
+    monkeypatch.setattr(fake_lib, "pnr_mlp_packed_t_bytes", lambda desc: 64, raising=False)
+
+    def pack_t(w, packed, buf_t, nbytes, stream):
+        fake_lib.packs_t += 1
+        return 0
+
+    monkeypatch.setattr(fake_lib, "pnr_mlp_pack_t", pack_t, raising=False)
+    net = _net()
+    m = net.mlp_coarse
+    names = ("_pnr_pack", "_pnr_pack_t", "_pnr_proj")
+    with torch.no_grad():
+        _, buf, buf_t = m.packed_t(net.code, "f16x3")
+        proj = net.hip_proj(True)
+        assert (fake_lib.packs, fake_lib.packs_t, fake_lib.projs) == (1, 1, 1)
+        for name in names:
+            rec = m.__dict__[name]
+            assert type(rec) is models._DeviceCache and rec.owner() is m and m._cached(name) is rec
+            assert rec.key == m._pack_key(net.code, None if name == "_pnr_proj" else "f16x3")
+        assert m.__dict__["_pnr_pack"].buffers[1] is buf and m.__dict__["_pnr_pack_t"].buffers[1] is buf_t
+        assert m.__dict__["_pnr_proj"].buffers[1] is proj
+        assert m.__dict__["_pnr_proj"].latent() is net.encoder.latent_cl
+        assert m.__dict__["_pnr_proj"].version == net.encoder.latent_cl._version
+        assert m.__dict__["_pnr_pack"].latent is None and m.__dict__["_pnr_pack_t"].version is None
+        # a replica holds the three records and is refused every one
+        rep = emulate_replicate(net)
+        rm = rep.mlp_coarse
+        for name in names:
+            assert rm.__dict__[name] is m.__dict__[name] and rm._cached(name) is None
+        _, rbuf, rbuf_t = rm.packed_t(rep.code, "f16x3")
+        rproj = rep.hip_proj(True)
+        assert rbuf is not buf and rbuf_t is not buf_t and rproj is not proj
+        assert (fake_lib.packs, fake_lib.packs_t, fake_lib.projs) == (2, 2, 2)
+        for name in names:
+            assert rm._cached(name).owner() is rm and m._cached(name).owner() is m
+        # so is a module that was handed another module's records, even under its own key
+        other = net.mlp_fine
+        for name in names:
+            other.__dict__[name] = m.__dict__[name]._replace(
+                key=other._pack_key(net.code, None if name == "_pnr_proj" else "f16x3"))
+            assert other._cached(name) is None
+        _, obuf, obuf_t = other.packed_t(net.code, "f16x3")
+        assert obuf is not buf and obuf_t is not buf_t and net.hip_proj(False) is not proj
+        assert (fake_lib.packs, fake_lib.packs_t, fake_lib.projs) == (3, 3, 3)
+        # a record whose owner is gone is nobody's
+        dead = m.__dict__["_pnr_pack"]._replace(owner=weakref.ref(torch.nn.Identity()))
+        m.__dict__["_pnr_pack"] = dead
+        assert m._cached("_pnr_pack") is None
+        # the original's other records were never touched
+        assert m.packed_t(net.code, "f16x3")[2] is buf_t and net.hip_proj(True) is proj
 
 
 def test_replica_parameters_and_grad_mode():

@@ -1295,7 +1295,7 @@ def test_bind_parallel_replicas_render_fixture():
     r.streams = tuple(st)
     with torch.no_grad():
         ref = r(net, arr["rays"].to(DEV), want_weights=True)   # the original packs + projects
-    orig_pack = net.mlp_coarse.__dict__["_pnr_pack"][3]
+    orig_pack = net.mlp_coarse.__dict__["_pnr_pack"].buffers[1]
     wrapped = _RenderWrapper(net, r, simple_output=False)
     reps = replicate(wrapped, [0, 0], detach=True)
     B = arr["rays"].shape[1]
@@ -1308,8 +1308,8 @@ def test_bind_parallel_replicas_render_fixture():
             o = rep(arr["rays"][:, lo:hi].to(DEV), want_weights=True)
         m = rep.net.mlp_coarse
         own = m.__dict__["_pnr_pack"]
-        assert own[0]() is m and own[3] is not orig_pack, "replica %d reused the original's pack" % i
-        assert m.__dict__["_pnr_proj"][0]() is m
+        assert own.owner() is m and own.buffers[1] is not orig_pack, "replica %d reused the original's pack" % i
+        assert m.__dict__["_pnr_proj"].owner() is m
         parts.append(o)
     torch.cuda.synchronize()
     out = DotMap({p: DotMap({k: torch.cat([o[p][k] for o in parts], 1) for k in parts[0][p]})

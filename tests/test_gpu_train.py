@@ -378,6 +378,78 @@ def test_training_noise_std_draw_order_matches_reference():
     assert torch.isfinite(lat.grad).all()
 
 
+def test_composite_backward_takes_expanded_output_gradients():
+    """The gradients autograd hands Composite.backward need not be dense: those of ``x.sum()`` are
+    stride-0 expansions of one element.  The backward launches on dense copies, each of which must
+    stay alive until the launch is queued (a copy freed early gives its block to the next one, and
+    two of the kernel's pointers then name the same memory): the result equals, bit for bit, the
+    one from dense gradients of the same values."""
+    from pnr.train import Composite
+
+    g = torch.Generator().manual_seed(11)
+    B, K = 37, 14
+    rays = torch.cat([torch.randn(B, 6, generator=g), torch.full((B, 1), 0.8), torch.full((B, 1), 1.8)], 1).to(DEV)
+    z = torch.sort(0.8 + torch.rand(B, K, generator=g), -1)[0].to(DEV).requires_grad_(True)
+    raw = torch.rand(B, K, 4, generator=g).to(DEV).requires_grad_(True)
+    got = {}
+    for dense in (True, False):
+        w, rgb, depth = Composite.apply(z, raw, rays, True)
+        if dense:
+            loss = (w * torch.full_like(w, 0.25)).sum() + (rgb * torch.ones_like(rgb)).sum() + \
+                (depth * torch.full_like(depth, 0.5)).sum()
+        else:
+            loss = 0.25 * w.sum() + rgb.sum() + 0.5 * depth.sum()
+        got[dense] = torch.autograd.grad(loss, (z, raw))
+    torch.cuda.synchronize()
+    for a, b, name in zip(got[True], got[False], ("d_z", "d_raw")):
+        assert torch.isfinite(a).all() and float(a.abs().max()) > 0, name
+        assert torch.equal(a, b), "%s: max |d| %g" % (name, float((a - b).abs().max()))
+
+
+def test_callback_noise_std_draw_order_matches_reference():
+    """The twin of the test above for the callback path (a conf the fused kernel refuses: softplus
+    blocks), same shape: under autograd in training mode with noise_std > 0 the generator is
+    consumed as u_coarse, coarse noise, u_fine, u_fine_jit, n_depth, fine noise (the callback draws
+    its sigma noise with randn_like)."""
+    cs = case(sb=1, rays_per_obj=4, kc=8, kf=6, kfd=2)
+    cf = conf()
+    cf["mlp_coarse"]["beta"] = cf["mlp_fine"]["beta"] = 1.0
+    net = PixelNeRFNet(cf)
+    assert net.fused_conf_reason() is not None
+    net.load_state_dict(cs["sd"], strict=False)
+    net = net.to(DEV)
+    lat = cs["latent"][:1].to(DEV).requires_grad_(True)
+    net.encode_latent(lat, cs["poses"][:1].to(DEV), cs["focal"][:1].to(DEV), (cs["width"], cs["height"]),
+                      c=cs["c"][:1].to(DEV), num_objs=1)
+    r = NeRFRenderer(n_coarse=8, n_fine=6, n_fine_depth=2, noise_std=0.5, white_bkgd=True).to(DEV).train()
+    log = []
+    rand, randn, randn_like = torch.rand, torch.randn, torch.randn_like
+
+    def lrand(*s, **k):
+        log.append(("rand", tuple(s[0]) if isinstance(s[0], (tuple, list)) else tuple(s)))
+        return rand(*s, **k)
+
+    def lrandn(*s, **k):
+        log.append(("randn", tuple(s[0]) if isinstance(s[0], (tuple, list)) else tuple(s)))
+        return randn(*s, **k)
+
+    def lrandn_like(t, **k):
+        log.append(("randn", tuple(t.shape)))
+        return randn_like(t, **k)
+
+    torch.rand, torch.randn, torch.randn_like = lrand, lrandn, lrandn_like
+    try:
+        out = r(net, cs["rays"][:1].to(DEV), want_weights=True)
+    finally:
+        torch.rand, torch.randn, torch.randn_like = rand, randn, randn_like
+    B = 4
+    assert log == [("rand", (B, 8)), ("randn", (B, 8)), ("rand", (B, 4)), ("rand", (B, 4)),
+                   ("randn", (B, 2)), ("randn", (B, 14))], log
+    loss = out.fine.rgb.sum() + out.coarse.rgb.sum()
+    loss.backward()
+    assert torch.isfinite(lat.grad).all()
+
+
 @pytest.mark.parametrize("rays_per_obj,K,ns,comb,n_blocks", [
     pytest.param(96, 41, 1, 3, 5, id="96-41-1-3"), pytest.param(256, 64, 1, 3, 5, id="256-64-1-3"),
     pytest.param(40, 41, 3, 3, 5, id="40-41-3-3"), pytest.param(256, 64, 2, 3, 5, id="256-64-2-3"),

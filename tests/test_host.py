@@ -50,6 +50,52 @@ def test_abi_version_and_error_channel():
     assert 13 * 512 * 512 * 4 < sz < 13 * 512 * 512 * 4 + 600000
 
 
+def test_call_passes_the_stream_last_and_raises_on_a_status(monkeypatch):
+    """_lib.call(name, device, *args): the named function gets the arguments and then the device's
+    current stream, with that device current; a status of 0 returns, any other raises PnrError
+    naming the function, the status and pnr_last_error().  A stub library: nothing is launched."""
+    seen = []
+
+    class Stub:
+        def pnr_good(self, *args):
+            seen.append(("good", guard[-1], args))
+            return 0
+
+        def pnr_bad(self, *args):
+            seen.append(("bad", guard[-1], args))
+            return -3
+
+        def pnr_last_error(self):
+            return b"the stub said no"
+
+    guard = [None]
+
+    class Guard:
+        def __init__(self, dev):
+            self.dev = dev
+
+        def __enter__(self):
+            guard.append(self.dev)
+
+        def __exit__(self, *exc):
+            guard.pop()
+            return False
+
+    monkeypatch.setattr(_lib, "load", lambda: Stub())
+    monkeypatch.setattr(_lib, "stream_of", lambda dev: ("stream of", dev))
+    monkeypatch.setattr(torch.cuda, "device", Guard)
+    assert _lib.call("pnr_good", "cuda:1", 1, None, 2.5) is None
+    assert seen == [("good", "cuda:1", (1, None, 2.5, ("stream of", "cuda:1")))]
+    assert _lib.call("pnr_good", "cuda:0") is None   # no arguments: the stream alone
+    assert seen[-1] == ("good", "cuda:0", (("stream of", "cuda:0"),))
+    with pytest.raises(_lib.PnrError, match=r"^pnr_bad failed \(status -3\): the stub said no$"):
+        _lib.call("pnr_bad", "cuda:0", 7)
+    assert seen[-1] == ("bad", "cuda:0", (7, ("stream of", "cuda:0")))
+    assert guard == [None]   # the device guard is left, also on the way out of a failure
+    with pytest.raises(AttributeError):
+        _lib.call("pnr_absent", "cuda:0")   # a missing entry point is an error, never a skipped launch
+
+
 def test_ops_refuse_cpu_tensors():
     with pytest.raises(ValueError, match="HIP device"):
         ops.composite(torch.zeros(2, 3), torch.zeros(2, 3, 4), torch.zeros(2, 8), True)

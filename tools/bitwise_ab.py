@@ -16,6 +16,10 @@ in another process, which changes the latent in its last bits.
                                                 (march_cases below): composite, the samplers, the draws, the ray
                                                 generator, the composite and point-input backward, and two renders
                                                 whose fine pass reuses the coarse MLP
+  python tools/bitwise_ab.py save-glue OUT.pt   the Python layer above the ABI, by names every revision of it has, so the
+                                                file also runs from an older checkout against one library (glue_cases
+                                                below): the training and callback renders with their gradients, point
+                                                queries, the sampler / mesh / image wrappers, refusals
   python tools/bitwise_ab.py cmp A.pt B.pt      bitwise equal? (torch.equal per tensor, no tolerance)
   python tools/bitwise_ab.py time OUT.json      HIP-event times of one render of 8,192 rays x (64 + 64)
                                                 per instantiation no bench leg reaches: one warm-up,
@@ -523,6 +527,208 @@ def save_march(out):
     print("saved", out, len(blob), "values", os.environ.get("PNR_LIB_PATH", "default"))
 
 
+# ---- the fifth case set: the Python layer above the ABI ----------------------------------------------
+# (n_coarse, n_fine, n_fine_depth); the last is a fine pass over the coarse samples (using_fine, n_fine set to 0)
+GLUE_SAMPLES = ((8, 6, 2), (8, 2, 2), (8, 6, 0), (8, 0, 0))
+
+
+def glue_cases():
+    """Yields (name, tensor or string): the paths of the Python layer that the other sets do not reach, through
+    names every revision of it has.  37 rays, one and two source views, a 32 x 32 synthetic latent.  A refused call
+    yields its exception's class and text; where the text is this layer's own wording of a library refusal, the class
+    alone ("refused class")."""
+    import numpy as np
+    import torch
+
+    import mc_ref
+    import mesh_ref
+    import meshclean_ref
+    import raster_ref
+    import test_gpu_mlp_lean as tl
+    import test_gpu_parity as tgp
+    from pnr import _lib, encoder, ops, synth, util
+    from pnr.models import PixelNeRFNet, ResnetFC
+    from pnr.renderer import NeRFRenderer
+
+    dev = torch.device("cuda:0")
+    rays37 = synth.scene_nmr(seed=3, n_rays=37)["rays"].to(dev).contiguous()
+
+    def refusal(fn, text=True):
+        try:
+            fn()
+        except Exception as e:   # noqa: BLE001  (a refusal is a result to compare)
+            return "%s: %s" % (type(e).__name__, e) if text else type(e).__name__
+        return "not refused"
+
+    def encode(net, ns):
+        """One object of ns views; the latent is a leaf, so its gradient is a result."""
+        lat = synth.latent(3, ns, 512, 32, 32).to(dev).requires_grad_(True)
+        poses = synth.srn_poses([20.0 * i for i in range(ns)], phi=-20.0, radius=2.7).reshape(1, ns, 4, 4)
+        net.encode_latent(lat, poses.to(dev), synth.scene_nmr(seed=3, n_rays=1)["focal"].to(dev), (64, 64), num_objs=1)
+        return lat
+
+    def renderer(samples, noise):
+        kc, kf, kfd = samples
+        r = NeRFRenderer(n_coarse=kc, n_fine=max(kf, 1), n_fine_depth=kfd, noise_std=noise, white_bkgd=True).to(dev)
+        r.n_fine = kf   # (8, 0, 0): using_fine stays set
+        r.return_z = True
+        return r.train()
+
+    def rendered(name, net, lat, r, grad):
+        """The outputs of one render under torch.manual_seed and, with ``grad``, the gradients of a fixed scalar."""
+        torch.manual_seed(13)
+        with torch.enable_grad() if grad else torch.no_grad():
+            out = r(net, rays37[None], want_weights=True)
+        loss = 0.0
+        for p in ("coarse", "fine"):
+            for k, wgt in (("rgb", 1.0), ("depth", 0.5), ("weights", 0.25), ("z", None)):
+                t = out[p][k]
+                yield "%s | %s.%s" % (name, p, k), t.detach().cpu()
+                if wgt is not None:   # a ramp per element: the gradient that reaches the composite is a dense tensor
+                    loss = loss + (t * torch.linspace(wgt, 2.0 * wgt, t.numel(), device=dev).reshape(t.shape)).sum()
+        if grad:
+            yield from grads(name, net, lat, loss)
+
+    def grads(name, net, lat, loss):
+        net.zero_grad()
+        lat.grad = None
+        loss.backward()
+        torch.cuda.synchronize()
+        for k, p in net.named_parameters():
+            if k.startswith("mlp_"):
+                yield "%s | d %s" % (name, k), (p.grad.cpu() if p.grad is not None else "no gradient")
+        yield "%s | d latent (atomic scatter)" % name, (lat.grad.cpu() if lat.grad is not None else "no gradient")
+
+    # (a) NeRFRenderer._forward_train: the fused conf with trainable parameters, training mode
+    for ns in (1, 2):
+        net = tl.make_net("f16x3", True)
+        lat = encode(net, ns)
+        for samples in GLUE_SAMPLES:
+            for noise in (0.0, 0.5):
+                yield from rendered("train ns%d %s noise %.1f" % (ns, samples, noise), net, lat, renderer(samples, noise),
+                                    True)
+
+    # (b) NeRFRenderer._forward_callback: a conf the fused kernel refuses (use_code_viewdirs), on its initial weights
+    cf = tgp.model_conf()
+    cf["use_code_viewdirs"] = True
+    for ns in (1, 2):
+        torch.manual_seed(0)
+        net = PixelNeRFNet(cf).to(dev).eval()
+        yield "callback ns%d | why not fused" % ns, str(net.fused_conf_reason())
+        lat = encode(net, ns)
+        for samples in GLUE_SAMPLES:
+            for noise in (0.0, 0.5):
+                for grad in (True, False):
+                    yield from rendered("callback ns%d %s noise %.1f grad%d" % (ns, samples, noise, grad), net, lat,
+                                        renderer(samples, noise), grad)
+
+    # (c) PixelNeRFNet.forward as a point query of 200 points: no_grad, autograd, xyz.requires_grad
+    for ns in (1, 2):
+        net = tl.make_net("f16x3", True)
+        lat = encode(net, ns)
+        xyz = torch.from_numpy(synth.hash_sym(77, (1, 200, 3), 0.5)).to(dev)
+        vd = torch.nn.functional.normalize(torch.from_numpy(synth.hash_sym(78, (1, 200, 3), 1.0)), dim=-1).to(dev)
+        for coarse in (True, False):
+            name = "query ns%d coarse%d" % (ns, coarse)
+            with torch.no_grad():
+                yield name + " no_grad | out", net(xyz, coarse=coarse, viewdirs=vd).cpu()
+            out = net(xyz, coarse=coarse, viewdirs=vd)
+            yield name + " autograd | out", out.detach().cpu()
+            yield from grads(name + " autograd", net, lat, (out * out).sum())
+            x = xyz.clone().requires_grad_(True)
+            out = net(x, coarse=coarse, viewdirs=vd)
+            yield name + " xyz.requires_grad | out", out.detach().cpu()
+            yield from grads(name + " xyz.requires_grad", net, lat, (out * out).sum())
+            yield name + " xyz.requires_grad | d xyz", x.grad.cpu()
+
+    # (d) the sampler and composite wrappers, the draws, the ray generator, the channels-last latent
+    g = torch.Generator().manual_seed(9)
+    u_c, u_f, u_j, n_d = (t.to(dev) for t in synth.rng_streams(5, 37, 8, 6, 2))
+    z_c = ops.sample_coarse(rays37, 8, u_c, False)
+    raw = torch.rand(37, 8, 4, generator=g).to(dev)
+    w, rgb, depth = ops.composite(z_c, raw, rays37, True)
+    yield "sample_coarse", z_c.cpu()
+    for k, t in (("weights", w), ("rgb", rgb), ("depth", depth)):
+        yield "composite | %s" % k, t.cpu()
+    yield "composite no weights | rgb", ops.composite(z_c, raw, rays37, False, want_weights=False)[1].cpu()
+    yield "sample_fine", ops.sample_fine(rays37, z_c, w, depth, 6, 2, 0.01, u_f, u_j, n_d, False).cpu()
+    yield "sample_fine lindisp no depth", ops.sample_fine(rays37, z_c, w, depth, 4, 0, 0.01, u_f, u_j, None, True).cpu()
+    yield "rng_fill", ops.rng_fill(1234, 3, _lib.RNG_U_FINE, 5, 37, dev).cpu()
+    yield "gen_rays", util.gen_rays(synth.srn_poses([10.0, 130.0], phi=-20.0, radius=2.7).to(dev), 7, 5,
+                                    torch.tensor([9.5, 9.25]), 0.8, 1.8, c=torch.tensor([3.4, 2.6])).cpu()
+    for nhwc in (True, False):
+        maps = [torch.randn(2, c, h, h, generator=g).to(dev) for c, h in ((5, 8), (3, 4), (4, 2))]
+        if nhwc:
+            maps = [t.contiguous(memory_format=torch.channels_last) for t in maps]
+        maps = [t.requires_grad_(True) for t in maps]
+        out = encoder.LatentChannelsLast.apply(*maps)
+        yield "latent_channels_last nhwc%d | out" % nhwc, out.detach().cpu()
+        (out * torch.randn(out.shape, generator=g).to(dev)).sum().backward()
+        for i, t in enumerate(maps):
+            yield "latent_channels_last nhwc%d | d map %d" % (nhwc, i), t.grad.contiguous().cpu()
+
+    # (e) the mesh and image wrappers, one call each
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    verts, faces = ops.marching_cubes(up(mc_ref.sphere_grid((9, 8, 7), (4.2, 3.6, 3.1), 2.4)), 0.0)
+    yield "marching_cubes | verts", verts.cpu()
+    yield "marching_cubes | faces", faces.cpu()
+    x, y = torch.rand(2, 23, 29, 3, generator=g).to(dev), torch.rand(2, 23, 29, 3, generator=g).to(dev)
+    for k, t in zip(("psnr", "ssim"), ops.image_metrics(x, y)):
+        yield "image_metrics | %s" % k, t.cpu()
+    v, f = (up(a) for a in mesh_ref.icosphere(1, 0.8))
+    for k, t in zip(("points", "normals", "tri", "area"), ops.mesh_sample(v, f, 100, seed=7)):
+        yield "mesh_sample | %s" % k, t.cpu()
+    pts = ops.box_sample((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), 150, seed=3, device=dev)
+    yield "box_sample", pts.cpu()
+    for k, t in zip(("d2", "idx"), ops.nearest(pts, v)):
+        yield "nearest | %s" % k, t.cpu()
+    yield "winding_number", ops.winding_number(v, f, pts).cpu()
+    rv, rf = (up(a) for a in raster_ref.sphere_with_floater(1))
+    poses = up(raster_ref.golden_poses(2, 1.3))
+    face, depth = ops.mesh_raster(rv, rf, poses, 16, 16, 16.4, c=8.0)
+    yield "mesh_raster | face", face.cpu()
+    yield "mesh_raster | depth", depth.cpu()
+    rgb, normal = ops.mesh_shade(rv, rf, poses, 16, 16, 16.4, face, depth, c=8.0, lights=((2.0, 1.0, 3.0),),
+                                 weights=(0.7,), want_normal=True)
+    yield "mesh_shade | rgb", rgb.cpu()
+    yield "mesh_shade | normal", normal.cpu()
+    yield "mesh_shade no lights | rgb", ops.mesh_shade(rv, rf, poses, 16, 16, 16.4, face, depth, c=8.0)[0].cpu()
+    sv, sf = (up(a) for a in meshclean_ref.soup(*mesh_ref.icosphere(1, 0.8)))
+    for k, t in zip(("verts", "faces", "remap"), ops.mesh_weld(sv, sf)):
+        yield "mesh_weld | %s" % k, t.cpu()
+    vl, fl, n_c = ops.mesh_components(rv, rf)
+    yield "mesh_components | vert_label", vl.cpu()
+    yield "mesh_components | face_label", fl.cpu()
+    yield "mesh_components | count", str(n_c)
+    for k, t in sorted(ops.mesh_component_stats(rv, rf, vl, fl).items()):
+        yield "mesh_component_stats | %s" % k, t.cpu()
+
+    # (f) refusals: a size the library refuses (no launch), and arguments this layer refuses
+    yield "refused marching_cubes 1025", refusal(lambda: ops.marching_cubes(torch.zeros(1025, 1, 1, device=dev), 0.0))
+    yield "refused image_metrics 8193", refusal(lambda: ops.image_metrics(torch.zeros(1, 8193, 7, 1, device=dev),
+                                                                          torch.zeros(1, 8193, 7, 1, device=dev)))
+    yield "refused mesh_raster 8193", refusal(lambda: ops.mesh_raster(rv, rf, poses, 8193, 1, 16.4))
+    yield "refused sample_coarse cpu", refusal(lambda: ops.sample_coarse(rays37.cpu(), 8, u_c))
+    yield "refused composite float64", refusal(lambda: ops.composite(z_c.double(), raw, rays37, True))
+    yield "refused box_sample cpu", refusal(lambda: ops.box_sample((0, 0, 0), (1, 1, 1), 4, device="cpu"))
+    yield "refused mesh_shade lights", refusal(lambda: ops.mesh_shade(rv, rf, poses, 16, 16, 16.4, face, depth,
+                                                                      lights=((1.0, 2.0),), weights=(1.0,)))
+    net = tl.make_net("fp32", True)
+    encode(net, 1)
+    yield "refused render cpu rays", refusal(lambda: renderer((8, 6, 2), 0.0)(net, rays37[None].cpu()))
+    narrow = ResnetFC(42, d_latent=256, d_hidden=256).to(dev)
+    yield "refused class pack of a 256-wide MLP", refusal(lambda: narrow.packed(net.code, "fp32"), text=False)
+    yield "refused class transposed pack in fp32", refusal(lambda: net.mlp_coarse.packed_t(net.code, "fp32"), text=False)
+
+
+def save_glue(out):
+    import torch
+
+    blob = dict(glue_cases())
+    torch.save(blob, out)
+    print("saved", out, len(blob), "values", os.environ.get("PNR_LIB_PATH", "default"))
+
+
 def cmp(a, b):
     import torch
 
@@ -543,7 +749,8 @@ def cmp(a, b):
         if len(A) <= 16:
             print(k, "identical" if eq else "max|d| %.3e" % float((A[k] - B[k]).abs().max()))
         elif not eq:
-            print(k, "DIFFERENT:", ("max|d| %.3e" % float((A[k].double() - B[k].double()).abs().max()))
+            print(k, "DIFFERENT:", ("max|d| %.3e of max|a| %.3e" % (float((A[k].double() - B[k].double()).abs().max()),
+                                                                    float(A[k].double().abs().max())))
                   if torch.is_tensor(A[k]) and torch.is_tensor(B[k]) and A[k].shape == B[k].shape else (A[k], B[k]))
     print("%d values compared" % n)
     print("BITWISE IDENTICAL" if same else "DIFFERENT")
@@ -648,5 +855,5 @@ if __name__ == "__main__":
     mode = sys.argv[1]
     if mode == "cmp":
         sys.exit(cmp(sys.argv[2], sys.argv[3]))
-    sys.exit({"save": save, "save-all": save_all, "save-train": save_train, "save-march": save_march, "time": time_cases,
-              "time-march": time_march}[mode](sys.argv[2]))
+    sys.exit({"save": save, "save-all": save_all, "save-train": save_train, "save-march": save_march,
+              "save-glue": save_glue, "time": time_cases, "time-march": time_march}[mode](sys.argv[2]))
